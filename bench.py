@@ -17,7 +17,12 @@ run N independent replicas ("replicas only"); value is the frames of 
 the max-over-ranks wall time.  The global-BA leg is ONE problem keyframe-block sharded over
 the N ranks with an RCCL exchange per LM trial (strong scaling, reported in `global_ba`).
 
-Prints ONE JSON line (rank 0) with roofline + cpu_baseline objects.
+A plain run sets up, warms up, times --steps steps and prints ONE JSON line (rank 0) with the
+headline (`value`, `ms_per_step`) and the timed steps' own statistics.  --full runs every other
+leg after the timed steps and adds it to the line: the host-input pipeline, the roofline passes,
+the batch-1 latency legs, local and global BA, RANSAC, the CPU baselines (`roofline`,
+`cpu_baseline`, `local_ba`, `global_ba`, ... objects).  --dump-outputs DIR writes what the last
+timed step's tracking chain returned as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -48,8 +53,18 @@ def parse():
     ap.add_argument("--gpus", type=int, default=None, help="GPUs (one rank each); default: WORLD_SIZE or 1")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check without a GPU: ranks meet over gloo and rank 0 prints n_gpus")
-    ap.add_argument("--steps", type=int, default=60)
+    ap.add_argument("--steps", type=int, default=60, help="timed steps of the stereo pipeline")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other leg and put it into the line: the host-input "
+                         "pipeline, the isolated roofline passes, the batch-1 latency legs, local and global BA, "
+                         "RANSAC, the CPU baselines, and the pipeline at 2000 features and sequence-shaped (fresh "
+                         "processes).  Without it the run sets up, warms up, times --steps steps and prints the "
+                         "headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step's tracking chain returned (keypoints, "
+                         "descriptors, stereo matches, map-point matches, poses, outlier flags, counts) as "
+                         "DIR/<name>.npy, float32 / float64, at most 64 MB in all")
     ap.add_argument("--batch", type=int, default=64, help="stereo frames per step")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU-baseline sample")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -207,6 +222,27 @@ def _coherent_host_f32(n):
     t = torch.frombuffer(buf, dtype=torch.float32, count=n)
     t.zero_()
     return t
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every array of `arrays` (float32 / float64, rows along axis 0) as
+    DIR/<name>.npy.  Over DUMP_LIMIT_BYTES in all, every array keeps the same fraction of its
+    rows, a fixed seeded choice in ascending order, so two runs with the same arguments write the
+    same rows and two builds can be compared output for output."""
+    out = Path(dirname)
+    out.mkdir(parents=True, exist_ok=True)
+    total = sum(a.nbytes + 128 for a in arrays.values())
+    keep = min(1.0, 0.98 * DUMP_LIMIT_BYTES / total)
+    rng = np.random.default_rng(64)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        if keep < 1.0:
+            rows = np.sort(rng.choice(a.shape[0], max(1, int(a.shape[0] * keep)), replace=False))
+            a = a[rows]
+        np.save(out / f"{name}.npy", np.ascontiguousarray(a))
 
 
 def relabel_valu(e, note):
@@ -1360,6 +1396,50 @@ def main():
             check(L.ORBmatcher_set_deferred(ln.m._h, 0), "ORBmatcher_set_deferred")
         return out
 
+    def lane_outputs(lane):
+        """What a caller of the timed step holds for the batch `lane` tracked last, as float arrays
+        (--dump-outputs): the Frame members of its B stereo pairs (mvKeys / mDescriptors of both
+        images, mvuRight, mvDepth), the new map points, and per tracked pair mvpMapPoints (local-map
+        rows), mTcw and mvbOutlier after TrackWithMotionModel's and after TrackLocalMap's
+        PoseOptimization, with the counts every call returned.  Rows past a frame's keypoint count
+        were never written and are zeroed.  Integers are stored by value (all below 2^24; a
+        descriptor as eight 32-bit words in float64)."""
+        torch.cuda.synchronize()
+        col = np.arange(cap)
+        vL = col[None, :] < np.asarray(lane.nL)[:, None]   # (B, cap): the left image's keypoint rows
+        vR = col[None, :] < np.asarray(lane.nR)[:, None]
+
+        def host(t, valid):
+            a = t.cpu().numpy().copy()
+            a[~valid] = 0
+            return a
+
+        def keys(t, valid):   # cv::KeyPoint records: five float fields, then octave and class_id
+            raw = host(t, valid)
+            a = raw.view(np.float32).copy()
+            a[..., 5:] = raw[..., 5:]
+            return a.reshape(-1, 7)
+
+        def descs(t, valid):
+            return host(t, valid).view("<u4").astype(np.float64).reshape(-1, 8)
+
+        f32 = lambda t, valid: host(t, valid).astype(np.float32)
+        vP = vL[1:]   # the tracked pairs' current frames
+        has_mp = host(lane.d_slot, vL) >= 0
+        cnt = lambda a: np.asarray(a, np.float64).copy()
+        return {"keypoints_left": keys(lane.d_kps, vL), "descriptors_left": descs(lane.d_desc, vL),
+                "keypoints_right": keys(lane.d_kpsR, vR), "descriptors_right": descs(lane.d_descR, vR),
+                "u_right": f32(lane.d_uR, vL), "depth": f32(lane.d_depth, vL),
+                "new_map_points": f32(lane.d_mp_pos, vL & has_mp).reshape(-1, 3),
+                "map_point_rows": f32(lane.d_cur_mp[1:], vP),
+                "pose_motion_model": f32(lane.d_Tout, np.ones(P, bool)),
+                "pose_local_map": f32(lane.d_Tout2, np.ones(P, bool)),
+                "outlier_motion_model": f32(lane.d_poutl, vP), "outlier_local_map": f32(lane.d_poutl2, vP),
+                "n_keypoints_left": cnt(lane.nL), "n_keypoints_right": cnt(lane.nR),
+                "n_stereo_matches": cnt(lane.nst), "n_matches_last_frame": cnt(lane.nm),
+                "n_matches_local_map": cnt(lane.nml), "n_visible_local_map": cnt(lane.nvis),
+                "n_inliers_motion_model": cnt(lane.ninl), "n_inliers_local_map": cnt(lane.ninl2)}
+
     def stage_by_stream():
         """Extraction stage ms per step by extractor stream (--stereo-batch: one stream, both images)."""
         per = {side: {k: round(v / args.steps, 4) for k, v in d.items()} for side, d in stage_lr.items()}
@@ -1397,7 +1477,12 @@ def main():
         print("k_select sections (cycles, problem 0, summed over the timed steps):", list(buf)[:16], file=sys.stderr)
     # the last timed chain's counts (its device work finished inside the timed region), then the
     # batch extracted by the last timed step, tracked outside it
+    last_lane = state["pending"]   # the lane whose chain the last timed step enqueued
     got += drain()[:1] if args.steps else []
+    if args.dump_outputs and rank == 0:
+        if last_lane is None:
+            sys.exit("bench.py: --dump-outputs needs at least one timed step (--steps >= 1)")
+        dump_outputs(args.dump_outputs, lane_outputs(last_lane))
     tot_kp = sum(r[0] for r in got)
     tot_match = sum(r[1] for r in got)
     tot_stereo = sum(r[2] for r in got)
@@ -1414,7 +1499,7 @@ def main():
     frames_total = P * args.steps * world
     fps = frames_total / dt
     host_io = None
-    if args.steps and not args.latency_only and not args.passes_only:
+    if args.steps and (args.full or args.pipeline_only) and not args.latency_only and not args.passes_only:
         host_io = host_io_pass(min(args.steps, 30))
     if args.latency_only:
         if rank == 0:
@@ -1446,6 +1531,40 @@ def main():
                                 "from the previous steps' estimates (device-side, no host round trip), so each step's "
                                 "tracking chain waits for the previous step's")
             json_out.write(json.dumps(line) + "\n")
+            json_out.flush()
+        if world > 1:
+            dist.destroy_process_group()
+        return
+
+    def headline():
+        """The result line of the timed steps alone; --full adds the other legs' objects to it."""
+        return {
+            "metric": METRIC, "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "u8",
+            "data": "synthetic (seeded KITTI-shaped textured stereo frames: camera-rotation motion, "
+                    "ground-plane disparity field 4..40 px)",
+            "config": {"workload": "kitti00_stereo: ORB extract L+R, ComputeStereoMatches, "
+                                   "TrackWithMotionModel (UpdateLastFrame, SearchByProjection(Cur,Last,th=7), "
+                                   "PoseOptimization), TrackLocalMap (isInFrustum + SearchByProjection(F, local map "
+                                   f"of the last {K_LOCAL} frames' map points, th=1) + PoseOptimization)",
+                       "width": W, "height": H,
+                       "nfeatures": NFEAT, "nlevels": 8, "scale_factor": 1.2, "fast_th": [20, 7],
+                       "stereo_frames_per_step": B, "tracked_frames_per_step": P, "parallelism": f"replicas{world}",
+                       "extractor_cu_reserve": args.reserve_cus},
+            "matches_per_s": round(tot_match / dt, 1), "stereo_matches_per_s": round(tot_stereo / dt, 1),
+            "keypoints_per_image": round(tot_kp / (2 * B * args.steps * world), 1),
+            "pose_inliers_per_frame": round(float(np.sum(pose_inl)) / max(len(pose_inl) * P, 1), 1),
+            "local_map_matches_per_frame": round(float(sum(a for a, _ in local_acc)) / max(len(local_acc) * P, 1), 1),
+            "local_map_visible_per_frame": round(float(sum(b for _, b in local_acc)) / max(len(local_acc) * P, 1), 1),
+            "stage_ms_per_step": {k: round(v / args.steps, 4) for k, v in stage_acc.items()},
+            "stage_ms_per_step_by_image": stage_by_stream(),
+            "phase_ms_per_step": {k: round(v / args.steps, 4) for k, v in phase_acc.items()},
+        }
+
+    if not args.full and not args.passes_only:   # the plain run: the timed steps' line and nothing else
+        if rank == 0:
+            json_out.write(json.dumps(dict(headline(), full=False)) + "\n")
             json_out.flush()
         if world > 1:
             dist.destroy_process_group()
@@ -1567,34 +1686,15 @@ def main():
         except Exception as e:  # noqa: BLE001 -- reported in the line, the headline stands
             seqline = {"error": f"{type(e).__name__}: {e}"}
     if rank == 0:
-        stage_ms = {k: round(v / args.steps, 4) for k, v in stage_acc.items()}
-        out = {
-            "metric": METRIC, "value": round(fps, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u8",
-            "data": "synthetic (seeded KITTI-shaped textured stereo frames: camera-rotation motion, "
-                    "ground-plane disparity field 4..40 px)",
-            "config": {"workload": "kitti00_stereo: ORB extract L+R, ComputeStereoMatches, "
-                                   "TrackWithMotionModel (UpdateLastFrame, SearchByProjection(Cur,Last,th=7), "
-                                   "PoseOptimization), TrackLocalMap (isInFrustum + SearchByProjection(F, local map "
-                                   f"of the last {K_LOCAL} frames' map points, th=1) + PoseOptimization)",
-                       "width": W, "height": H,
-                       "nfeatures": NFEAT, "nlevels": 8, "scale_factor": 1.2, "fast_th": [20, 7],
-                       "stereo_frames_per_step": B, "tracked_frames_per_step": P, "parallelism": f"replicas{world}", "extractor_cu_reserve": args.reserve_cus},
+        out = dict(headline(), full=True)
+        out.update({
             "sequence_frames_per_s": round(1000.0 / latency["host_path"]["p50_ms"], 1),
             "sequence_frames_per_s_note": "one SLAM sequence (frames in order, batch 1) through the drop-in host "
                                           "path: 1000 / latency.host_path.p50_ms; `value` is batch throughput",
-            "matches_per_s": round(tot_match / dt, 1), "stereo_matches_per_s": round(tot_stereo / dt, 1),
-            "keypoints_per_image": round(tot_kp / (2 * B * args.steps * world), 1),
-            "pose_inliers_per_frame": round(float(np.sum(pose_inl)) / max(len(pose_inl) * P, 1), 1),
-            "local_map_matches_per_frame": round(float(sum(a for a, _ in local_acc)) / max(len(local_acc) * P, 1), 1),
-            "local_map_visible_per_frame": round(float(sum(b for _, b in local_acc)) / max(len(local_acc) * P, 1), 1),
-            "stage_ms_per_step": stage_ms,
-            "stage_ms_per_step_by_image": stage_by_stream(),
-            "phase_ms_per_step": {k: round(v / args.steps, 4) for k, v in phase_acc.items()}, "roofline": roof,
+            "roofline": roof,
             "matcher_roofline": mroof, "latency": latency, "cpu_baseline": cpu, "local_ba": ba,
             "global_ba": gba, "ransac": ransac, "nfeatures_2000": nf2000, "sequence_pipeline": seqline,
-        }
+        })
         if host_io is not None:
             host_io["frac_of_value"] = round(host_io["value"] / fps, 3)
             out["value_host_io"] = host_io

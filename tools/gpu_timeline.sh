@@ -11,7 +11,7 @@ mkdir -p "$OUT"
 cd "$R" || exit 1
 export TMPDIR=/tmp
 ORBGPU_LBA_STREAMS=1 timeout -k 10 400 rocprofv3 --kernel-trace --memory-copy-trace --stats -f csv -d "$OUT/prof" -o bench -- \
-  python3 "$R/bench.py" --no-cpu-baseline --steps 20 "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
+  python3 "$R/bench.py" --full --no-cpu-baseline --steps 20 "$@" > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
 python3 tools/prof_csv.py "$(find "$OUT/prof" -name '*kernel_stats.csv' | head -1)" 40 > "$OUT/kernel_stats.txt"
 python3 tools/timeline.py "$(find "$OUT/prof" -name '*kernel_trace.csv' | head -1)" 8 > "$OUT/timeline.txt"
 cat "$OUT/timeline.txt"

@@ -18,11 +18,11 @@ if [ -z "$2" ]; then
   cat "$OUT/smoke.txt"
 fi
 echo "[r05] bench" && date
-timeout -k 10 900 python bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
+timeout -k 10 900 python bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
 python3 -c "import json,sys; d=json.load(open(sys.argv[1])); r=d['roofline']; print(d['value'], d['ms_per_step'], r['kernel'], r['avg_launch_ms'], r['frac'], d.get('sequence_frames_per_s'))" "$OUT/bench.json"
 echo "[r05] rocprofv3" && date
 ORBGPU_LBA_STREAMS=1 timeout -k 10 600 rocprofv3 --kernel-trace --stats -f csv -d "$OUT/prof" -o bench -- \
-  python3 "$R/bench.py" --no-cpu-baseline > "$OUT/bench_prof.json" 2> "$OUT/bench_prof.err" || { tail -30 "$OUT/bench_prof.err"; exit 1; }
+  python3 "$R/bench.py" --full --no-cpu-baseline > "$OUT/bench_prof.json" 2> "$OUT/bench_prof.err" || { tail -30 "$OUT/bench_prof.err"; exit 1; }
 KS=$(find "$OUT/prof" -name '*kernel_stats.csv' | head -1)
 KT=$(find "$OUT/prof" -name '*kernel_trace.csv' | head -1)
 python3 tools/prof_csv.py "$KS" 60 > "$OUT/kernel_stats.txt"

@@ -15,6 +15,6 @@ if [ $# -gt 0 ]; then
   tail -2 "$OUT/pytest.txt"
 fi
 if [ -z "$NOBENCH" ]; then
-  timeout -k 10 900 python bench.py $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
+  timeout -k 10 900 python bench.py --full $BENCH_ARGS > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
   python3 -c "import json,sys; d=json.load(open(sys.argv[1])); print(d['value'], d['ms_per_step'], d.get('value_host_io'), d['latency']['p50_ms'], d['latency']['host_path']['p50_ms'], d['local_ba'].get('single_stream'), d['global_ba'].get('value'))" "$OUT/bench.json"
 fi

@@ -3,7 +3,7 @@
 headline; k_fast_cells, its `secondary`) is the last `launches` full-size launches of its kernel
 in the run; average their kernel-trace durations and compare with the bench's HIP-event figure.
 
-usage: roofline_check.py kernel_trace.csv bench.json
+usage: roofline_check.py kernel_trace.csv bench.json   (bench.json: the line of `bench.py --full`)
 """
 import csv
 import json
