@@ -8,11 +8,17 @@
 //   per active edge: quadratic-form terms SoA (Hpp 21 | bp 6 | Hll 9 | bl 3),
 //   Hpl 6x3 AoS, BDinv 6x3 AoS, B*db 6; per pose Hpp/bp; per landmark Hll/bl/Dinv/db;
 //   dense Schur system S (6 nP)^2 (upper triangle used).
-// Kernels per LM solve():  k_linearize (edge ||) -> k_pose_reduce (workgroup per pose)
-//   + k_land_reduce (wave per landmark) -> [k_lambda_init] ; per trial:
-//   k_point_prep (thread per landmark) -> k_schur (workgroup per pose block)
-//   -> k_ldlt (one workgroup) -> k_update (thread per vertex) -> k_errors (edge ||)
-//   -> k_csum2 (canonical chi2 and computeScale) ; host reads 4 scalars, decides.
+// This file holds the BA pipeline: BaEngine (upload, structure, LM drivers) and its kernels, and
+// the unit entry points of their building blocks.  The dense single-workgroup LDL^T lives in
+// ldlt_dense.hip, the block-sparse one in ldlt.hip, Optimizer::PoseOptimization in pose_opt.hip;
+// the device helpers they share are in ba_math.hpp.
+// Kernels per LM solve():  k_linearize (edge ||) + k_chi2_finish -> k_pose_reduce (workgroup
+//   per pose) + k_land_reduce (thread per landmark entry) -> [k_lambda_init] ; per trial:
+//   k_point_prep (thread per pose-list entry) -> k_schur (workgroup or wave per pose block)
+//   -> the LDL^T solve (dense_ldlt_launch, or SparseLdlt::solve from 24 free poses)
+//   -> k_update (thread per vertex) -> k_linearize + k_chi2_finish (the trial's chi2)
+//   -> k_scale (computeScale) ; the host reads the scalars and decides (lm_solve), or
+//   k_lm_trial_end decides on the device (optimize_device, whose steps fuse some of these).
 // Every accumulation uses the canonical 64-wide tree order (oracle/ba.c ora_csum),
 // so results are bit-identical to the CPU restatement.
 #include "ba.hpp"
@@ -39,38 +45,6 @@
 #include "orb_common.hpp"
 
 namespace orbgpu {
-
-
-__device__ __forceinline__ void se3_exp(const double* upd, Se3& out) {
-    const double* w = upd;
-    const double* u = upd + 3;
-    const double theta = sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
-    const double Om[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
-    double Om2[9], R[9], V[9];
-    for (int i = 0; i < 3; i++)
-        for (int j = 0; j < 3; j++)
-            Om2[i * 3 + j] = (Om[i * 3] * Om[j] + Om[i * 3 + 1] * Om[3 + j]) + Om[i * 3 + 2] * Om[6 + j];
-    if (theta < 0.00001) {
-        for (int i = 0; i < 9; i++) {
-            R[i] = (((i % 4) == 0 ? 1.0 : 0.0) + Om[i]) + Om2[i];
-            V[i] = R[i];
-        }
-    } else {
-        double s, c;
-        detmath::sincos_d(theta, &s, &c);
-        const double a = s / theta, b = (1 - c) / (theta * theta);
-        const double cc = (theta - s) / ((theta * theta) * theta);
-        for (int i = 0; i < 9; i++) {
-            const double I = (i % 4) == 0 ? 1.0 : 0.0;
-            R[i] = (I + a * Om[i]) + b * Om2[i];
-            V[i] = (I + b * Om[i]) + cc * Om2[i];
-        }
-    }
-    quat_from_R(R, out.q);
-    for (int i = 0; i < 3; i++) out.t[i] = (V[i * 3] * u[0] + V[i * 3 + 1] * u[1]) + V[i * 3 + 2] * u[2];
-    out.pad = 0;
-    se3_normalize(out);
-}
 
 // computeError (types_six_dof_expmap.h:94-99, 126-131; .cpp:141-157)
 __device__ __forceinline__ void edge_error(const EdgeDev& e, const Se3& T, const double* X, double* err) {
@@ -129,16 +103,6 @@ __device__ __forceinline__ double wave_trees(const double* v, double* buf) {
     return r;
 }
 
-
-constexpr int DIAG21[6] = {0, 6, 11, 15, 18, 20};
-
-// Device-resident LM (BaEngine::optimize_device): every kernel of a step takes a gate word that
-// k_lm_trial_end set for it; a step the decision made unnecessary runs as empty launches.
-// nullptr: always run (the host-driven path).
-#define BA_GATE(run)                  \
-    do {                              \
-        if ((run) && !*(run)) return; \
-    } while (0)
 
 // term layout (SoA, stride nE): Hpp 0..20 | bp 21..26 | Hll 27..35 | bl 36..38
 constexpr int T_HPP = 0, T_BP = 21, T_HLL = 27, T_BL = 36, T_N = 39;
@@ -886,847 +850,6 @@ static void schur_launch(int nBlk, int ldc, hipStream_t st, A... args) {
         hipLaunchKernelGGL(k_schur<512>, dim3(nBlk), dim3(512), 0, st, args..., kChunks);
 }
 
-// Dense LDL^T of the upper triangle + solve, one workgroup (256 threads).
-// Same per-element operation sequence as oracle ora_ldlt_solve, blocked by 6-column panels:
-// wave 0 factorises the panel rows and writes L (lower triangle), then every wave
-// applies the panel's rank-1 updates, in k order, to its trailing rows.
-__global__ void __launch_bounds__(256) k_ldlt(int n, double* Sg, const double* bs, double* x, double* scal, int in_lds,
-                                              const int* run) {
-    BA_GATE(run);
-    extern __shared__ double lds[];
-    double* y = lds;            // n
-    double* A = in_lds ? lds + n : Sg;
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    __shared__ int ok;
-    if (in_lds)
-        for (int q = tid; q < n * n; q += blockDim.x) A[q] = Sg[q];
-    for (int q = tid; q < n; q += blockDim.x) y[q] = bs[q];
-    if (tid == 0) ok = 1;
-    __syncthreads();
-    for (int p0 = 0; p0 < n; p0 += 6) {
-        const int p1 = min(p0 + 6, n);
-        if (w == 0) {
-            for (int k = p0; k < p1; k++) {
-                const double d = A[(size_t)k * n + k];
-                if (d == 0.0) {
-                    if (lane == 0) ok = 0;
-                    break;
-                }
-                for (int i = k + 1 + lane; i < n; i += 64) A[(size_t)i * n + k] = A[(size_t)k * n + i] / d;
-                __builtin_amdgcn_wave_barrier();
-                for (int i = k + 1; i < p1; i++) {
-                    const double li = A[(size_t)i * n + k];
-                    for (int j = i + lane; j < n; j += 64) A[(size_t)i * n + j] -= li * A[(size_t)k * n + j];
-                }
-                __builtin_amdgcn_wave_barrier();
-            }
-        }
-        __syncthreads();
-        if (!ok) break;
-        for (int i = p1 + w; i < n; i += 4) {
-            double L[6];
-            for (int k = p0; k < p1; k++) L[k - p0] = A[(size_t)i * n + k];
-            for (int j = i + lane; j < n; j += 64) {
-                double v = A[(size_t)i * n + j];
-                for (int k = p0; k < p1; k++) v -= L[k - p0] * A[(size_t)k * n + j];
-                A[(size_t)i * n + j] = v;
-            }
-        }
-        __syncthreads();
-    }
-    if (!ok) {
-        if (tid == 0) scal[3] = 0.0;
-        return;
-    }
-    if (w == 0) {
-        // L y = b: per row, subtractions in k order (column-sweep order of the oracle)
-        for (int r0 = 0; r0 < n; r0 += 64) {
-            const int i = r0 + lane;
-            double acc = i < n ? y[i] : 0.0;
-            for (int k = 0; k < r0; k++)
-                if (i < n) acc -= A[(size_t)i * n + k] * y[k];
-            for (int k = r0; k < min(r0 + 64, n); k++) {
-                const double yk = __shfl(acc, k - r0, 64);
-                if (i > k && i < n) acc -= A[(size_t)i * n + k] * yk;
-            }
-            if (i < n) y[i] = acc;
-            __builtin_amdgcn_wave_barrier();
-        }
-        for (int k = lane; k < n; k += 64) y[k] = y[k] / A[(size_t)k * n + k];
-        __builtin_amdgcn_wave_barrier();
-        // L^T x = z: per row, subtractions in descending k order
-        for (int r1 = n; r1 > 0; r1 -= 64) {
-            const int r0 = max(r1 - 64, 0);
-            const int i = r0 + lane;
-            double acc = i < r1 ? y[i] : 0.0;
-            for (int k = n - 1; k >= r1; k--)
-                if (i < r1) acc -= A[(size_t)k * n + i] * y[k];
-            for (int k = r1 - 1; k >= r0; k--) {
-                const double yk = __shfl(acc, k - r0, 64);
-                if (i < k) acc -= A[(size_t)k * n + i] * yk;
-            }
-            if (i < r1) y[i] = acc;
-            __builtin_amdgcn_wave_barrier();
-        }
-        for (int k = lane; k < n; k += 64) x[k] = y[k];
-        if (lane == 0) scal[3] = 1.0;
-    }
-}
-
-__device__ __forceinline__ double readlane_d(double v, int l) {
-    const unsigned long long u = __double_as_longlong(v);
-    const int lo = __builtin_amdgcn_readlane((int)(u & 0xffffffffu), l);
-    const int hi = __builtin_amdgcn_readlane((int)(u >> 32), l);
-    return __longlong_as_double(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-
-// z = D^-1 y, then L^T x = z (per row, subtractions in descending k order; L[k][i] =
-// Lall[i * n + k]) by one wave; y is overwritten.  The oracle's ora_ldlt_solve sequence.
-__device__ __forceinline__ void ldlt_backward_wave(int n, const double* Lall, const double* dvec, double* y, double* x,
-                                                   double* scal) {
-    const int lane = threadIdx.x & 63;
-    for (int k = lane; k < n; k += 64) y[k] = y[k] / dvec[k];
-    __builtin_amdgcn_wave_barrier();
-    for (int r1 = n; r1 > 0; r1 -= 64) {
-        const int r0 = max(r1 - 64, 0);
-        const int i = r0 + lane;
-        const bool on = i < r1;
-        const int ic = on ? i : r0;
-        double acc = on ? y[i] : 0.0;
-        int k = n - 1;
-        for (; k - 8 >= r1 - 1; k -= 8) {
-            double L8[8], Y8[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                L8[u] = Lall[(size_t)ic * n + (k - u)];
-                Y8[u] = y[k - u];
-            }
-#pragma unroll
-            for (int u = 0; u < 8; u++) acc -= L8[u] * Y8[u];
-        }
-        for (; k >= r1; k--) acc -= Lall[(size_t)ic * n + k] * y[k];
-        k = r1 - 1;
-        for (; k - 8 >= r0 - 1; k -= 8) {
-            double L8[8];
-#pragma unroll
-            for (int u = 0; u < 8; u++) L8[u] = Lall[(size_t)ic * n + (k - u)];
-#pragma unroll
-            for (int u = 0; u < 8; u++) {
-                const double yk = readlane_d(acc, k - u - r0);
-                if (i < k - u) acc -= L8[u] * yk;
-            }
-        }
-        for (; k >= r0; k--) {
-            const double yk = readlane_d(acc, k - r0);
-            if (i < k) acc -= Lall[(size_t)ic * n + k] * yk;
-        }
-        if (on) y[i] = acc;
-        __builtin_amdgcn_wave_barrier();
-    }
-    for (int k = lane; k < n; k += 64) x[k] = y[k];
-    if (lane == 0) scal[3] = 1.0;
-}
-
-// Row-owner LDL^T + forward substitution for n <= kLdltRowMax (16 free keyframes: a local BA),
-// two waves.  Thread i holds row i of [S | b] (its upper part, j >= i) in registers.  At pivot
-// k, row k -- final after its k updates -- sits in LDS (published by its owner at the end of
-// pivot k - 1, double-buffered); every row i > k forms l_ik = u_ki / d_k and subtracts
-// l_ik * u_kj from each of its entries, k ascending per element: the oracle's ora_ldlt_solve
-// sequence (the right-hand side, column n, runs the forward substitution y_i -= l_ik y_k).
-// Row k + 1 then publishes itself: one barrier per pivot, no panel round trips.
-constexpr int kLdltRowMax = 96;
-__global__ void __launch_bounds__(128) k_ldlt_row(int n, const double* __restrict__ Sg, const double* bs, double* x,
-                                                  double* scal, const int* run) {
-    BA_GATE(run);
-    __shared__ double Ur[2][kLdltRowMax + 1];   // published row k: entries j < n, b_k at [kLdltRowMax]
-    __shared__ double Lall[kLdltRowMax * kLdltRowMax];   // L[i][k] at Lall[k * n + i]
-    __shared__ double dvec[kLdltRowMax], y[kLdltRowMax];
-    const int i = threadIdx.x;
-    const bool mine = i < n;
-    double a[kLdltRowMax];
-#pragma unroll
-    for (int j = 0; j < kLdltRowMax; j++) a[j] = (mine && j < n && j >= i) ? Sg[(size_t)i * n + j] : 0.0;
-    double bi = mine ? bs[i] : 0.0;
-    if (i == 0) {
-#pragma unroll
-        for (int j = 0; j < kLdltRowMax; j++)
-            if (j < n) Ur[0][j] = a[j];
-        Ur[0][kLdltRowMax] = bi;
-    }
-    __syncthreads();
-    bool ok = true;
-    for (int k = 0; k < n; k++) {
-        const double* U = Ur[k & 1];
-        const double d = U[k];
-        if (d == 0.0) {   // uniform: every thread reads the same pivot
-            ok = false;
-            break;
-        }
-        if (i == 0) {
-            dvec[k] = d;
-            y[k] = U[kLdltRowMax];   // b_k after its k updates: forward-substituted y_k
-        }
-        if (i > k && mine) {
-            const double l = U[i] / d;
-            Lall[(size_t)k * n + i] = l;
-#pragma unroll
-            for (int c = 0; c < kLdltRowMax / 8; c++) {
-                if (8 * c + 7 < i) continue;
-#pragma unroll
-                for (int q = 0; q < 8; q++) {
-                    const int j = 8 * c + q;
-                    if (j >= i && j < n) a[j] -= l * U[j];
-                }
-            }
-            bi -= l * U[kLdltRowMax];
-            if (i == k + 1) {   // row k + 1 is final: publish it for the next pivot
-                double* V = Ur[(k + 1) & 1];
-#pragma unroll
-                for (int j = 0; j < kLdltRowMax; j++)
-                    if (j >= i && j < n) V[j] = a[j];
-                V[kLdltRowMax] = bi;
-            }
-        }
-        __syncthreads();
-    }
-    if (!ok) {
-        if (i == 0) scal[3] = 0.0;
-        return;
-    }
-    if (i >= 64) return;
-    ldlt_backward_wave(n, Lall, dvec, y, x, scal);
-}
-
-// Column-owner LDL^T + solve for n <= kLdltColMax (16 free keyframes: a local BA), 4 waves.
-// Lane c owns columns c and c + 64 of [S | b] (b in column n); wave w owns rows i = 4 r + w,
-// so a thread holds A[i][c] for its wave's rows in registers.  Pivot k: the pivot row (final
-// after k updates) sits in LDS, published by its owner at the end of pivot k - 1 (double-
-// buffered); every thread forms l_ck = u_kc / d_k for its columns (two lane-parallel quotients,
-// one reciprocal), the wave reads back the l of its own rows, and subtracts l_ik u_kj from its
-// rows, k ascending per element: the oracle's ora_ldlt_solve sequence (column n runs the
-// forward substitution y_i -= l_ik y_k).  The owner of row k + 1 updates that row first and
-// publishes it, one barrier per pivot.  The pivot loop is rolled: its body (24 rows x 2
-// columns) stays in the instruction cache, unlike a fully unrolled 90-pivot chain.
-constexpr int kLdltColMax = 96;
-constexpr int kLdltColRows = kLdltColMax / 4;
-__global__ void __launch_bounds__(256) k_ldlt_col(int n, const double* __restrict__ Sg, const double* bs, double* x,
-                                                  double* scal, const int* run) {
-    BA_GATE(run);
-    __shared__ double Ur[2][128];                        // published row k: columns 0..n (b at n)
-    __shared__ double Lall[kLdltColMax * kLdltColMax];   // L[i][k] at Lall[k * n + i]
-    __shared__ __attribute__((aligned(16))) double lw[4][kLdltColRows + 8];   // l_ik of wave w's rows (r = i / 4)
-    __shared__ double dvec[kLdltColMax], y[kLdltColMax];
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int c0 = lane, c1 = lane + 64;
-    double A0[kLdltColRows], A1[kLdltColRows];
-#pragma unroll
-    for (int r = 0; r < kLdltColRows; r++) {
-        const int i = 4 * r + w;
-        const bool row = i < n;
-        A0[r] = (row && c0 < n && c0 >= i) ? Sg[(size_t)i * n + c0] : (row && c0 == n) ? bs[i] : 0.0;
-        A1[r] = (row && c1 < n && c1 >= i) ? Sg[(size_t)i * n + c1] : (row && c1 == n) ? bs[i] : 0.0;
-    }
-    if (w == 0) {
-        Ur[0][c0] = A0[0];
-        Ur[0][c1] = A1[0];
-    }
-    __syncthreads();
-    bool ok = true;
-    for (int k = 0; k < n; k++) {
-        const double* U = Ur[k & 1];
-        double* V = Ur[(k + 1) & 1];
-        const double d = U[k];
-        if (d == 0.0) {   // uniform: every thread reads the same pivot
-            ok = false;
-            break;
-        }
-        const double u0 = U[c0], u1 = U[c1];
-        const int own = (k + 1) & 3;   // the wave of row k + 1
-        if (w == own) {
-            // row k + 1 first: its l from the broadcast u_{k,k+1} (the same quotient lane k + 1 forms)
-            const int r1 = (k + 1) >> 2;
-            const double l1 = U[k + 1 < n ? k + 1 : k] / d;
-#pragma unroll
-            for (int r = 0; r < kLdltColRows; r++)
-                if (r == r1 && k + 1 < n) {
-                    A0[r] -= l1 * u0;
-                    A1[r] -= l1 * u1;
-                    V[c0] = A0[r];
-                    V[c1] = A1[r];
-                }
-        }
-        // plain divisions: two cost 160 cycles, one reciprocal shared by two 324
-        // (tools/micro/ldlt_col.hip)
-        const double l0 = u0 / d, l1v = u1 / d;
-        if (w == 0) {
-            if (c0 > k && c0 < n) Lall[k * n + c0] = l0;
-            if (c1 > k && c1 < n) Lall[k * n + c1] = l1v;
-            if (lane == 0) {
-                dvec[k] = d;
-                y[k] = U[n];   // b_k after its k updates: the forward-substituted y_k
-            }
-        }
-        if ((lane & 3) == w) {   // the l of this wave's rows, c = 4 r + w
-            lw[w][lane >> 2] = l0;
-            lw[w][16 + (lane >> 2)] = l1v;
-        }
-        __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0): the wave's own LDS writes are visible
-        __builtin_amdgcn_wave_barrier();
-        // rows i = 4 r + w > k + 1 (row k + 1 was done above), four at a time: a group with a live
-        // row loads its four l together and updates branch-free (a branch per row serialised the
-        // LDS latency of every row: 2.1 k cycles per pivot, tools/micro/ldlt_col.hip)
-        const int rlive = (k + 5 - w) >> 2;   // first r with 4 r + w >= k + 2
-#pragma unroll
-        for (int g = 0; g < kLdltColRows / 4; g++) {
-            if (4 * g + 3 >= rlive && 16 * g + w < n) {
-                const double2 la = *reinterpret_cast<const double2*>(&lw[w][4 * g]);
-                const double2 lb = *reinterpret_cast<const double2*>(&lw[w][4 * g + 2]);
-                const double lv[4] = {la.x, la.y, lb.x, lb.y};
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int r = 4 * g + q, i = 4 * r + w;
-                    const bool live = i > k + 1 && i < n;
-                    const double v0 = A0[r] - lv[q] * u0, v1 = A1[r] - lv[q] * u1;
-                    A0[r] = live ? v0 : A0[r];
-                    A1[r] = live ? v1 : A1[r];
-                }
-            }
-        }
-        __syncthreads();
-    }
-    if (!ok) {
-        if (tid == 0) scal[3] = 0.0;
-        return;
-    }
-    if (w != 0) return;
-    ldlt_backward_wave(n, Lall, dvec, y, x, scal);
-}
-
-// Row-lane LDL^T + solve for n <= kLdltColMax, 4 waves: lane i owns rows i and i + 64 of
-// [S | b] (b in column n), wave w the columns j = 4 r + w (r <= 24).  Pivot k: the published row
-// k (final after k updates) sits in LDS, permuted so a wave's columns are contiguous; every lane
-// forms its rows' l_ik = u_ki / d_k itself (no l broadcast), reads u_kj of its wave's live
-// columns as broadcasts and subtracts l_ik u_kj, k ascending per element: the oracle's
-// ora_ldlt_solve sequence (column n runs the forward substitution).  Then lane k + 1 publishes
-// its row; one barrier per pivot.  Rows at or above the pivot and lower-triangle entries carry
-// values nobody reads, so the updates need no per-row predicate.
-constexpr int kLdltTCols = kLdltColMax / 4 + 1;   // 25 columns per wave: j <= 96 covers b at n <= 96
-__global__ void __launch_bounds__(256) k_ldlt_t(int n, const double* __restrict__ Sg, const double* bs, double* x,
-                                                double* scal, const int* run) {
-    BA_GATE(run);
-    __shared__ __attribute__((aligned(16))) double Up[2][4][kLdltTCols + 3];   // row k: Up[.][j & 3][j >> 2]
-    __shared__ double Lall[kLdltColMax * kLdltColMax];   // S staging, then L[i][k] at Lall[k * n + i]
-    __shared__ double dvec[kLdltColMax], y[kLdltColMax];
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int i0 = lane, i1 = lane + 64;
-    // S through LDS: coalesced global reads, then each lane its rows
-    for (int q = tid; q < n * n; q += 256) Lall[q] = Sg[q];
-    __syncthreads();
-    double A0[kLdltTCols], A1[kLdltTCols];
-#pragma unroll
-    for (int r = 0; r < kLdltTCols; r++) {
-        const int j = 4 * r + w;
-        A0[r] = (i0 < n && j < n && j >= i0) ? Lall[i0 * n + j] : (i0 < n && j == n) ? bs[i0] : 0.0;
-        A1[r] = (i1 < n && j < n && j >= i1) ? Lall[i1 * n + j] : (i1 < n && j == n) ? bs[i1] : 0.0;
-    }
-    if (lane == 0) {   // row 0
-#pragma unroll
-        for (int r = 0; r < kLdltTCols; r++) Up[0][w][r] = A0[r];
-    }
-    __syncthreads();   // the staging area is free for L from here
-    bool ok = true;
-    for (int k = 0; k < n; k++) {
-        const double(*U)[kLdltTCols + 3] = Up[k & 1];
-        const double d = U[k & 3][k >> 2];
-        if (d == 0.0) {   // uniform
-            ok = false;
-            break;
-        }
-        // this lane's rows: l = u_ki / d_k (rows <= k compute values nobody reads)
-        const double l0 = k < 63 ? U[i0 & 3][i0 >> 2] / d : 0.0;
-        const double l1 = n > 64 ? U[i1 & 3][i1 >> 2] / d : 0.0;
-        if (w == 0) {
-            if (i0 > k && i0 < n) Lall[k * n + i0] = l0;
-            if (i1 > k && i1 < n) Lall[k * n + i1] = l1;
-            if (lane == 0) {
-                dvec[k] = d;
-                y[k] = U[n & 3][n >> 2];   // b_k after its k updates: the forward-substituted y_k
-            }
-        }
-        // live columns j > k of this wave, four at a time (a uniform skip of dead groups)
-        const int rlive = (k + 4 - w) >> 2;   // first r with 4 r + w >= k + 1
-#pragma unroll
-        for (int g = 0; g < (kLdltTCols + 3) / 4; g++) {
-            if (4 * g + 3 >= rlive && 16 * g + w <= n) {
-                const double2 ua = *reinterpret_cast<const double2*>(&U[w][4 * g]);
-                const double2 ub = *reinterpret_cast<const double2*>(&U[w][4 * g + 2]);
-                const double uv[4] = {ua.x, ua.y, ub.x, ub.y};
-#pragma unroll
-                for (int q = 0; q < 4; q++) {
-                    const int r = 4 * g + q;
-                    if (r < kLdltTCols) {
-                        if (k < 63) A0[r] -= l0 * uv[q];
-                        if (n > 64) A1[r] -= l1 * uv[q];
-                    }
-                }
-            }
-        }
-        // row k + 1 is final: its lane publishes this wave's columns
-        const int kp = k + 1;
-        if (kp < n && (kp < 64 ? lane == kp : lane == kp - 64)) {
-            double* V = Up[kp & 1][w];
-            if (kp < 64) {   // two loops: a select of the arrays would move them to scratch
-#pragma unroll
-                for (int r = 0; r < kLdltTCols; r++) V[r] = A0[r];
-            } else {
-#pragma unroll
-                for (int r = 0; r < kLdltTCols; r++) V[r] = A1[r];
-            }
-        }
-        __syncthreads();
-    }
-    if (!ok) {
-        if (tid == 0) scal[3] = 0.0;
-        return;
-    }
-    if (w != 0) return;
-    ldlt_backward_wave(n, Lall, dvec, y, x, scal);
-}
-
-// 2-D block-cyclic LDL^T + solve for n <= kLdltColMax, 4 waves: thread (a, b) holds A[i][j] for
-// i = 16 r + a, j = 16 c + b of [S | b] (b in column n); a wave holds four row classes, so a
-// register row or column past the live part of the matrix is skipped by the whole wave.  Per
-// panel of 8 pivots: the owners publish the panel rows, wave 0 factors them right-looking
-// (lane = column: l_jk = u_kj / d_k lane-parallel, the later panel rows updated with the l read
-// back by readlane), writing the final U rows and the L columns to LDS, then every thread
-// applies the panel's pivots, ascending, to its live entries.  Per element the oracle's
-// ora_ldlt_solve sequence; two barriers per panel.
-constexpr int k2dPW = 8, k2dR = 6, k2dC = 7;   // panel width; rows 16 r + a (r < 6), columns 16 c + b (c < 7)
-__global__ void __launch_bounds__(256) k_ldlt_2d(int n, const double* __restrict__ Sg, const double* bs, double* x,
-                                                 double* scal, const int* run) {
-    BA_GATE(run);
-    __shared__ double Lall[kLdltColMax * kLdltColMax];   // S staging, then L[i][k] at Lall[k * n + i]
-    __shared__ double UP[k2dPW][128];                    // the panel's final U rows, columns 0..n
-    __shared__ double Pn[k2dPW][128];                    // the panel rows as published
-    __shared__ double dvec[kLdltColMax], y[kLdltColMax];
-    __shared__ int ok;
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    const int a = 4 * w + (lane & 3), b = lane >> 2;
-    for (int q = tid; q < n * n; q += 256) Lall[q] = Sg[q];
-    if (tid == 0) ok = 1;
-    __syncthreads();
-    double A[k2dR][k2dC];
-#pragma unroll
-    for (int r = 0; r < k2dR; r++)
-#pragma unroll
-        for (int c = 0; c < k2dC; c++) {
-            const int i = 16 * r + a, j = 16 * c + b;
-            A[r][c] = (i < n && j < n && j >= i) ? Lall[i * n + j] : (i < n && j == n) ? bs[i] : 0.0;
-        }
-    for (int p0 = 0; p0 < n; p0 += k2dPW) {
-        const int p1 = min(p0 + k2dPW, n);
-        // the panel rows' current values (final: every earlier panel is applied)
-#pragma unroll
-        for (int r = 0; r < k2dR; r++) {
-            const int i = 16 * r + a;
-            if (i >= p0 && i < p1)
-#pragma unroll
-                for (int c = 0; c < k2dC; c++) Pn[i - p0][16 * c + b] = A[r][c];
-        }
-        __syncthreads();   // also: every thread is done with the previous panel's UP
-        if (w == 0) {
-            double u0[k2dPW], u1[k2dPW];
-#pragma unroll
-            for (int t = 0; t < k2dPW; t++) {
-                u0[t] = p0 + t < n ? Pn[t][lane] : 0.0;
-                u1[t] = p0 + t < n ? Pn[t][lane + 64] : 0.0;
-            }
-            bool good = true;
-#pragma unroll
-            for (int t = 0; t < k2dPW; t++) {
-                const int k = p0 + t;
-                if (k < n && good) {
-                    UP[t][lane] = u0[t];   // row k is final
-                    UP[t][lane + 64] = u1[t];
-                    const double d = k < 64 ? readlane_d(u0[t], k) : readlane_d(u1[t], k - 64);
-                    if (d == 0.0) {   // uniform
-                        good = false;
-                        if (lane == 0) ok = 0;
-                    } else {
-                        const double l0 = u0[t] / d, l1 = u1[t] / d;   // l_jk, j = lane / lane + 64
-                        if (lane > k && lane < n) Lall[k * n + lane] = l0;
-                        if (lane + 64 > k && lane + 64 < n) Lall[k * n + lane + 64] = l1;
-                        const double yk = n < 64 ? readlane_d(u0[t], n) : readlane_d(u1[t], n - 64);
-                        if (lane == 0) {
-                            dvec[k] = d;
-                            y[k] = yk;   // b_k after its k updates: the forward-substituted y_k
-                        }
-#pragma unroll
-                        for (int t2 = t + 1; t2 < k2dPW; t2++) {
-                            const int i = p0 + t2;
-                            if (i < n) {
-                                const double li = i < 64 ? readlane_d(l0, i) : readlane_d(l1, i - 64);
-                                u0[t2] -= li * u0[t];
-                                u1[t2] -= li * u1[t];
-                            }
-                        }
-                    }
-                }
-            }
-        }
-        __syncthreads();
-        if (!ok) break;
-        // rows >= p1: the panel's pivots, ascending, on the live register rows / columns
-        const int pw = p1 - p0;
-#pragma unroll
-        for (int r = 0; r < k2dR; r++) {
-            if (16 * r + 4 * w + 3 < p1) continue;   // the wave's four rows of register row r are done
-            const int i = 16 * r + a;
-            double lv[k2dPW];
-#pragma unroll
-            for (int t = 0; t < k2dPW; t++) lv[t] = t < pw ? Lall[(p0 + t) * n + i] : 0.0;
-#pragma unroll
-            for (int c = 0; c < k2dC; c++) {
-                if (16 * c + 15 < p1) continue;      // every column of register column c is done
-                const int j = 16 * c + b;
-                double v = A[r][c];
-#pragma unroll
-                for (int t = 0; t < k2dPW; t++)
-                    if (t < pw) v -= lv[t] * UP[t][j];
-                A[r][c] = v;
-            }
-        }
-    }
-    if (!ok) {
-        if (tid == 0) scal[3] = 0.0;
-        return;
-    }
-    __syncthreads();
-    if (w != 0) return;
-    ldlt_backward_wave(n, Lall, dvec, y, x, scal);
-}
-
-// The dense LDL^T of the local BA's reduced system (k_ldlt_reg, below).
-#ifdef ORB_LDLT_PROBE
-__device__ long long g_ldlt_probe[256];
-#define LDLT_PROBE(slot) \
-    do {                                                  \
-        if (threadIdx.x == 0) g_ldlt_probe[slot] = clock64(); \
-    } while (0)
-#else
-#define LDLT_PROBE(slot) \
-    do {                 \
-    } while (0)
-#endif
-constexpr int kLdltMax = 128;
-constexpr int kTiledMinPoses = kBaTiledMinPoses;   // 6 x 24 = 144 rows: the first n the LDS-resident dense solver cannot hold
-constexpr int kDenseMaxN = 144;   // >= every n the dense single-workgroup solvers take (n^2 doubles in LDS)
-constexpr int kLdltWaves = 8;     // 512 threads: 256 VGPRs per lane, the panel registers stay unspilled
-constexpr int kLdltThreads = 64 * kLdltWaves;
-// LDS of k_ldlt_reg: Lall (n x n), three 6 x kLdltMax panel row buffers, two kLdltMax x 6 panel L
-// buffers, d, y
-static inline size_t ldlt_reg_shm(int n) { return sizeof(double) * ((size_t)n * n + 1 + 32 * kLdltMax); }
-
-// SharedDiv::div without its branch: the quotient of an in-range numerator, or a * r for a zero
-// one (a / b = a signed zero); any other numerator (or an out-of-range divisor) sets `bad` and the
-// caller redoes the work with SharedDiv::div.
-__device__ __forceinline__ double div_fast(const SharedDiv& d, double a, bool& bad) {
-    const double q = a * d.r;
-    const double rem = fma(-d.b, q, a);
-    const double res = __builtin_amdgcn_div_fixup(fma(rem, d.r, q), d.b, a);
-    const double aa = fabs(a);
-    const bool inr = aa > 0x1p-300 && aa < 0x1p300;
-    bad = bad || !(inr || aa == 0.0);
-    return inr ? res : q;
-}
-
-// the panel factorisation of k_ldlt_reg for one column thread j, any panel width pw <= 6, with
-// SharedDiv::div (the fallback of ldlt_panel6)
-__device__ __forceinline__ void ldlt_panel_generic(int n, int p0, int pw, int j, double* U, double* Lall,
-                                                   double* Lpan, double* dvec, double* y, int* ok) {
-    double Bk[6][6], Lb[6][6], dd[6];
-#pragma unroll
-    for (int t = 0; t < 6; t++)
-#pragma unroll
-        for (int c = 0; c < 6; c++) {
-            Bk[t][c] = (t < pw && c < pw && c >= t) ? U[t * kLdltMax + p0 + c] : 0.0;
-            Lb[t][c] = 0.0;
-        }
-    bool bad = false;
-    SharedDiv sd[6] = {SharedDiv(1.0), SharedDiv(1.0), SharedDiv(1.0), SharedDiv(1.0), SharedDiv(1.0),
-                       SharedDiv(1.0)};
-#pragma unroll
-    for (int t = 0; t < 6; t++) {
-        dd[t] = Bk[t][t];
-        if (t < pw) {
-            bad |= dd[t] == 0.0;
-            sd[t] = SharedDiv(dd[t]);
-#pragma unroll
-            for (int t2 = t + 1; t2 < 6; t2++)
-                if (t2 < pw) Lb[t2][t] = sd[t].div(Bk[t][t2]);
-#pragma unroll
-            for (int t2 = t + 1; t2 < 6; t2++)
-#pragma unroll
-                for (int c = t2; c < 6; c++)
-                    if (c < pw) Bk[t2][c] -= Lb[t2][t] * Bk[t][c];
-        }
-    }
-    double u[6];
-#pragma unroll
-    for (int t = 0; t < 6; t++) u[t] = t < pw ? U[t * kLdltMax + j] : 0.0;
-#pragma unroll
-    for (int t = 0; t < 6; t++) {
-        if (t < pw) {
-            const int k = p0 + t;
-            const bool act = j > k && j < n;
-            const double l = act ? sd[t].div(u[t]) : 0.0;
-#pragma unroll
-            for (int t2 = t + 1; t2 < 6; t2++)
-                if (t2 < pw && j >= p0 + t2) u[t2] -= Lb[t2][t] * u[t];
-            if (act) {
-                Lall[(size_t)k * n + j] = l;
-                Lpan[j * 6 + t] = l;
-            }
-            if (j == n) y[k] = u[t];   // row k's right-hand side is final: forward-substituted y_k
-        }
-    }
-#pragma unroll
-    for (int t = 0; t < 6; t++)
-        if (t < pw) U[t * kLdltMax + j] = u[t];
-    if (j == 0) {
-#pragma unroll
-        for (int t = 0; t < 6; t++)
-            if (t < pw) dvec[p0 + t] = dd[t];
-        if (bad) *ok = 0;
-    }
-}
-
-// A full panel (pw = 6) in one basic block: every thread first factorises the 6x6 diagonal block
-// from LDS itself (the same operations as the block's own columns perform, so d and the block's L
-// agree bit for bit), then its own column: l_jk = u_kj / d_k and u_tj -= L[t][k] u_kj, k
-// ascending.  Results stay in registers until the wave knows that every division was a fast one;
-// a wave with a zero pivot or an out-of-range operand redoes the panel with ldlt_panel_generic.
-__device__ __forceinline__ void ldlt_panel6(int n, int p0, int j, double* U, double* Lall, double* Lpan,
-                                            double* dvec, double* y, int* ok) {
-    double B[6][6], Lb[6][6], dd[6];
-#pragma unroll
-    for (int t = 0; t < 6; t++)
-#pragma unroll
-        for (int c = t; c < 6; c++) B[t][c] = U[t * kLdltMax + p0 + c];
-    double u[6];
-#pragma unroll
-    for (int t = 0; t < 6; t++) u[t] = U[t * kLdltMax + j];
-    bool bad = false;
-    SharedDiv sd[6] = {SharedDiv(1.0), SharedDiv(1.0), SharedDiv(1.0), SharedDiv(1.0), SharedDiv(1.0),
-                       SharedDiv(1.0)};
-#pragma unroll
-    for (int t = 0; t < 6; t++) {
-        dd[t] = B[t][t];
-        sd[t] = SharedDiv(dd[t]);
-        bad = bad || !sd[t].ok;
-#pragma unroll
-        for (int t2 = t + 1; t2 < 6; t2++) Lb[t2][t] = div_fast(sd[t], B[t][t2], bad);
-#pragma unroll
-        for (int t2 = t + 1; t2 < 6; t2++)
-#pragma unroll
-            for (int c = t2; c < 6; c++) B[t2][c] -= Lb[t2][t] * B[t][c];
-    }
-    double l[6];
-    bool badc = false;
-#pragma unroll
-    for (int t = 0; t < 6; t++) {
-        const bool act = j > p0 + t && j < n;
-        bool bt = false;
-        const double q = div_fast(sd[t], u[t], bt);
-        badc = badc || (act && bt);
-        l[t] = act ? q : 0.0;
-#pragma unroll
-        for (int t2 = t + 1; t2 < 6; t2++) {
-            const double v = u[t2] - Lb[t2][t] * u[t];
-            u[t2] = j >= p0 + t2 ? v : u[t2];
-        }
-    }
-    if (__ballot(bad || badc)) {
-        ldlt_panel_generic(n, p0, 6, j, U, Lall, Lpan, dvec, y, ok);
-        return;
-    }
-#pragma unroll
-    for (int t = 0; t < 6; t++) {
-        const int k = p0 + t;
-        if (j > k && j < n) {
-            Lall[(size_t)k * n + j] = l[t];
-            Lpan[j * 6 + t] = l[t];
-        }
-        U[t * kLdltMax + j] = u[t];
-    }
-    if (j == n)
-#pragma unroll
-        for (int t = 0; t < 6; t++) y[p0 + t] = u[t];   // forward-substituted y_k
-    if (j == 0)
-#pragma unroll
-        for (int t = 0; t < 6; t++) dvec[p0 + t] = dd[t];
-}
-
-// Row waves of k_ldlt_reg (waves 2..7, kRowWaves of them): wave 2 + t owns rows i = 6 r + t
-// (slot r < kRowSlots) of columns j = lane, lane + 64, so a 6-row panel p is slot p of every row
-// wave.  In phase p a row wave applies panel p - 1's six rank-one updates (its L from Lp, its
-// rows u from Up) in k order to its rows i >= 6 (p + 1) -- panel p's own rows were handed to the
-// factor waves one phase earlier -- and publishes slot p + 1 (panel p + 1's row, now updated by
-// every panel up to p - 1) to Un.  Rows i >= 64 own no column below 64 on or right of the
-// diagonal; column registers 64.. matter only for n >= 64 (the right-hand side sits at column n).
-constexpr int kRowWaves = 6;
-constexpr int kRowSlots = (kLdltMax + kRowWaves - 1) / kRowWaves;
-__device__ __forceinline__ void ldlt_rows(double (&R)[2][kRowSlots], const double* Up, const double* Lp, double* Un,
-                                          int n, int p1, int t6, int lane) {
-    double u0[6], u1[6];
-#pragma unroll
-    for (int t = 0; t < 6; t++) {
-        u0[t] = Up[t * kLdltMax + lane];
-        u1[t] = Up[t * kLdltMax + lane + 64];
-    }
-#pragma unroll
-    for (int r = 0; r < kRowSlots; r++) {
-        const int i = kRowWaves * r + t6;
-        if (i >= p1 && i < n) {
-            double L[6];
-#pragma unroll
-            for (int t = 0; t < 6; t++) L[t] = Lp[i * 6 + t];
-            if (i < 64) {
-                double v0 = R[0][r];
-#pragma unroll
-                for (int t = 0; t < 6; t++) v0 -= L[t] * u0[t];
-                R[0][r] = lane >= i ? v0 : R[0][r];
-            }
-            if (n >= 64) {
-                double v1 = R[1][r];
-#pragma unroll
-                for (int t = 0; t < 6; t++) v1 -= L[t] * u1[t];
-                R[1][r] = lane + 64 >= i ? v1 : R[1][r];
-            }
-            if (i < p1 + 6) {   // panel p + 1's row
-                Un[(i - p1) * kLdltMax + lane] = R[0][r];
-                Un[(i - p1) * kLdltMax + lane + 64] = R[1][r];
-            }
-        }
-    }
-}
-
-// Register-resident LDL^T + solve for n < 128 (<= 21 free keyframes), 512 threads, with a
-// one-panel lookahead: waves 0-1 factorise 6-column panels (one thread per column j), waves 2-7
-// hold the rows.  Phase p: the factor waves factorise panel p from its rows in LDS (every earlier
-// panel's updates applied) and signal; the row waves apply panel p - 1 to their rows below panel
-// p (the trailing update runs under the factorisation), publish panel p + 1's rows to LDS and,
-// once panel p is factored, apply panel p to those rows there (one row per wave, no register
-// indexing).  One barrier per phase; panel rows rotate through three buffers, panel L through
-// two.  Per-element operation sequence identical to oracle ora_ldlt_solve (every element receives
-// the pivots' updates in ascending k).
-__global__ void __launch_bounds__(kLdltThreads) k_ldlt_reg(int n, const double* __restrict__ Sg, const double* bs,
-                                                           double* x, double* scal, const int* run) {
-    BA_GATE(run);
-    extern __shared__ double lds[];
-    double* Lall = lds;                               // n x n, Lall[k * n + i] = L[i][k]
-    double* Ub = Lall + (((size_t)n * n + 1) & ~(size_t)1);   // 3 x (6 x kLdltMax) panel rows (16-B aligned)
-    double* Lb = Ub + 18 * kLdltMax;                  // 2 x (kLdltMax x 6) panel L
-    double* dvec = Lb + 12 * kLdltMax;                // n
-    double* y = dvec + kLdltMax;                      // n
-    __shared__ int ok, done;
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);   // wave-uniform: row branches stay scalar
-    const bool factor = w < kLdltMax / 64;
-    const int t6 = w - kLdltMax / 64;
-    // [S | b] (n <= 126 < kLdltMax): column n carries the right-hand side, so the row updates run
-    // the forward substitution L y = b with the oracle's sequence (y_i -= l_ik y_k, k ascending)
-    // and y_k is final when row k becomes a pivot row
-    double R[2][kRowSlots];
-    if (!factor) {
-#pragma unroll
-        for (int c = 0; c < 2; c++)
-#pragma unroll
-            for (int r = 0; r < kRowSlots; r++) {
-                const int i = kRowWaves * r + t6, j = lane + 64 * c;
-                R[c][r] = (i < n && j < n && i <= j) ? Sg[(size_t)i * n + j] : (i < n && j == n) ? bs[i] : 0.0;
-            }
-        if (t6 < n) {   // panel 0's rows (slot 0)
-            Ub[t6 * kLdltMax + lane] = R[0][0];
-            Ub[t6 * kLdltMax + lane + 64] = R[1][0];
-        }
-    }
-    LDLT_PROBE(0);
-    if (tid == 0) {
-        ok = 1;
-        done = 0;
-    }
-    __syncthreads();
-    LDLT_PROBE(1);
-    int cur = 0;   // panel p's row buffer: p mod 3
-    for (int p0 = 0; p0 < n; p0 += 6) {
-        const int p1 = min(p0 + 6, n), pw = p1 - p0, pi = p0 / 6;
-        const int prv = cur == 0 ? 2 : cur - 1, nxt = cur == 2 ? 0 : cur + 1;
-        double* U = Ub + cur * 6 * kLdltMax;
-        double* Un = Ub + nxt * 6 * kLdltMax;
-        double* Lpan = Lb + (pi & 1) * 6 * kLdltMax;
-        LDLT_PROBE(11 + 4 * (pi < 20 ? pi : 20));
-        if (factor) {
-            if (pw == 6) ldlt_panel6(n, p0, tid, U, Lall, Lpan, dvec, y, &ok);
-            else ldlt_panel_generic(n, p0, pw, tid, U, Lall, Lpan, dvec, y, &ok);
-            // (also after a zero pivot: the row waves wait for this count)
-            if (lane == 0) __hip_atomic_fetch_add(&done, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
-#ifdef ORB_LDLT_PROBE
-            if (tid == 0 && pi < 20) g_ldlt_probe[220 + pi] = clock64();   // factor done
-#endif
-        } else {
-            // panel p - 1's updates on the rows below panel p, panel p + 1's rows published.  The
-            // slot index is re-made opaque per panel: hoisted out of the panel loop, the rows'
-            // offsets and tests spill SGPRs into VGPR lanes (a v_readlane each per row)
-            int tv = t6;
-            asm volatile("" : "+s"(tv));
-            if (p0 > 0) {
-                ldlt_rows(R, Ub + prv * 6 * kLdltMax, Lb + ((pi & 1) ^ 1) * 6 * kLdltMax, Un, n, p1, tv, lane);
-            } else if (6 + t6 < n) {   // phase 0: panel 1's rows (slot 1) as they are
-                Un[t6 * kLdltMax + lane] = R[0][1];
-                Un[t6 * kLdltMax + lane + 64] = R[1][1];
-            }
-#ifdef ORB_LDLT_PROBE
-            if (lane == 0 && pi < 16) g_ldlt_probe[124 + 6 * pi + t6] = clock64();   // bulk done
-#endif
-            const int i = p1 + tv;   // this wave's row of panel p + 1 (panel p is full when it exists)
-            if (i < n) {
-                while (__hip_atomic_load(&done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < 2 * (pi + 1))
-                    __builtin_amdgcn_s_sleep(1);
-                double L[6], u0[6], u1[6];
-#pragma unroll
-                for (int t = 0; t < 6; t++) {
-                    L[t] = Lpan[i * 6 + t];
-                    u0[t] = U[t * kLdltMax + lane];
-                    u1[t] = U[t * kLdltMax + lane + 64];
-                }
-                double v0 = Un[tv * kLdltMax + lane], v1 = Un[tv * kLdltMax + lane + 64];
-                const double o0 = v0, o1 = v1;
-#pragma unroll
-                for (int t = 0; t < 6; t++) {
-                    v0 -= L[t] * u0[t];
-                    v1 -= L[t] * u1[t];
-                }
-                Un[tv * kLdltMax + lane] = lane >= i ? v0 : o0;
-                Un[tv * kLdltMax + lane + 64] = lane + 64 >= i ? v1 : o1;
-            }
-        }
-        __syncthreads();
-        LDLT_PROBE(12 + 4 * (pi < 20 ? pi : 20));
-        if (!ok) break;
-        cur = nxt;
-    }
-    LDLT_PROBE(2);
-    if (!ok) {
-        if (tid == 0) scal[3] = 0.0;
-        return;
-    }
-    if (w != 0) return;
-    LDLT_PROBE(3);
-    ldlt_backward_wave(n, Lall, dvec, y, x, scal);
-    LDLT_PROBE(4);
-}
-
 // push + back-substitution (block_solver.hpp:457-484) + SparseOptimizer::update (oplus)
 __global__ void __launch_bounds__(256) k_update(BaStructDev s, Se3* T, Se3* Tbak, double* X, double* Xbak,
                                                 double* x, const double* __restrict__ Hpl, const double* Hll,
@@ -2187,1183 +1310,8 @@ __global__ void __launch_bounds__(256) k_tile_unpack(int n, double* __restrict__
     }
 }
 
-// ---------------------------------------------------------------- PoseOptimization
-// Optimizer::PoseOptimization (Optimizer.cc:239-451): one SE3 vertex with unary
-// EdgeSE3ProjectXYZOnlyPose / EdgeStereoSE3ProjectXYZOnlyPose edges
-// (types_six_dof_expmap.cpp:266-364), solved by LinearSolverDense (Eigen LDLT with diagonal
-// pivoting).  The whole call -- 4 rounds of optimize(10), each restarted from mTcw, with the
-// outlier classification after every round -- is ONE persistent workgroup per frame (a batch
-// of frames is one launch).  Per LM iteration: one fused pass over the active edges (errors,
-// robust chi2 and the 27 terms of the 6x6 system, canonical 64-tree sums of oracle/ba.c),
-// then per trial the register-resident pivoted LDL^T + SE3 update on thread 0 and one error
-// pass.  Edges are 32 B (the reference's float inputs; converted to double on load) and each
-// wave prefetches its next chunk's edges while it computes the current one.
-struct PoseEdgeDev {
-    float Xw[3], obs[3];   // GetWorldPos(); kpUn.pt.x, .y, mvuRight
-    float info;            // mvInvLevelSigma2[octave]
-    int meta;              // bit 31: stereo edge; bits 0-30: keypoint index
-};
-
-struct PoseProbDev {
-    int ne, e0;            // edges E[e0 .. e0+ne)
-    int nbad, N;           // out: nBad of the last round (-1: < 3 correspondences)
-    Se3 T0;                // Converter::toSE3Quat(pFrame->mTcw)
-    Se3 T;                 // out
-    double fx, fy, cx, cy, bf;
-    // device mode: the frame's arrays in HBM (edges are built by k_pose_pack, results
-    // written back by k_pose_opt's epilogue); null in host mode
-    const float* Tcw;
-    const uint8_t* has_mp;
-    const float* Xw;
-    const float* obs;
-    const float* inv_sigma2;
-    float* Tcw_out;
-    uint8_t* outlier;
-    // frame mode (pose_frame): gathered by k_pose_pack instead of the packed arrays above
-    const int* mpidx;          // mvpMapPoints as indices (-1 NULL)
-    const float* mp_pos;       // map point rows (GetWorldPos)
-    const float* keys;         // mvKeysUn, 7 words per cv::KeyPoint (x y size angle response octave class_id)
-    const float* uR;           // mvuRight
-    const float* isig_tab;     // mvInvLevelSigma2
-    int nlev;
-    int* ninl;                 // optional device out: inliers (ne - nBad), 0 below 3 edges, -1 over capacity
-};
-
-// one edge in double (the g2o edge's _measurement / information / Huber delta)
-struct PoseEdgeD {
-    double X[3], obs[3], info, delta, dsqr;
-    bool stereo;
-};
-
-__device__ __forceinline__ PoseEdgeD pose_edge_load(const PoseEdgeDev* E, int i, double dM, double dS) {
-    const uint4* p = reinterpret_cast<const uint4*>(E + i);
-    const uint4 a = p[0], b = p[1];
-    PoseEdgeD e;
-    e.X[0] = (double)__uint_as_float(a.x);
-    e.X[1] = (double)__uint_as_float(a.y);
-    e.X[2] = (double)__uint_as_float(a.z);
-    e.obs[0] = (double)__uint_as_float(a.w);
-    e.obs[1] = (double)__uint_as_float(b.x);
-    e.obs[2] = (double)__uint_as_float(b.y);
-    e.info = (double)__uint_as_float(b.z);
-    e.stereo = (b.w >> 31) != 0;
-    e.delta = e.stereo ? dS : dM;   // RobustKernelHuber delta = sqrt(chi2 threshold) as float
-    e.dsqr = e.delta * e.delta;
-    return e;
-}
-
-// the error at camera point p (dz: the shared divisions by p[2])
-__device__ __forceinline__ void pose_err_p(const PoseEdgeD& e, const double* p, const SharedDiv& dz,
-                                           const PoseProbDev& P, double* err) {
-    if (!e.stereo) {
-        const double px = dz.div(p[0]), py = dz.div(p[1]);
-        err[0] = e.obs[0] - (px * P.fx + P.cx);
-        err[1] = e.obs[1] - (py * P.fy + P.cy);
-        err[2] = 0;
-    } else {
-        const float invz = (float)dz.div(1.0);
-        const double u = (p[0] * (double)invz) * P.fx + P.cx;
-        const double v = (p[1] * (double)invz) * P.fy + P.cy;
-        err[0] = e.obs[0] - u;
-        err[1] = e.obs[1] - v;
-        err[2] = e.obs[2] - (u - P.bf * (double)invz);
-    }
-}
-
-__device__ __forceinline__ void pose_err(const PoseEdgeD& e, const Se3& T, const PoseProbDev& P, double* err) {
-    double p[3];
-    se3_map(T, e.X, p);
-    pose_err_p(e, p, SharedDiv(p[2]), P, err);
-}
-
-__device__ __forceinline__ double pose_chi2(const PoseEdgeD& e, const double* err) {
-    double s = err[0] * (e.info * err[0]);
-    s += err[1] * (e.info * err[1]);
-    if (e.stereo) s += err[2] * (e.info * err[2]);
-    return s;
-}
-
-__device__ __forceinline__ double pose_rho0(const PoseEdgeD& e, double c, bool robust) {
-    if (!robust || c <= e.dsqr) return c;
-    const double sq = sqrt(c);
-    return (2 * sq) * e.delta - e.dsqr;
-}
-
-
-constexpr int kPoseMaxEdges = 8192;
-// two waves per SIMD (512 threads): half the chunks per wave in every edge pass (the same
-// canonical sums: bit-identical).  Measured in the pipeline beside the extraction grids too:
-// 28.8 k vs 28.1 k frames/s for the one-wave-per-SIMD instance (256 threads) at B = 64, so
-// every batch takes it; ORBGPU_POSE_WIDE_MAX = F keeps it for batches of at most F frames only
-constexpr int kPoseThreads = 256, kPoseThreadsWide = 512;
-static int pose_wide_max() {
-    static const int v = [] {
-        const char* e = getenv("ORBGPU_POSE_WIDE_MAX");
-        return e ? atoi(e) : (1 << 30);
-    }();
-    return v;
-}
-
-// Opt-in (ORBGPU_POSE_LDS_KB=n): reserve n KiB of LDS per pose workgroup in the chained batch
-// launch, so that the extraction grids' LDS-staged kernels cannot share the CUs the pose
-// workgroups run on (dynamic bytes added on top of the kernel's static LDS)
-static size_t pose_lds_pad(const void* fn) {
-    static const int kb = [] {
-        const char* e = getenv("ORBGPU_POSE_LDS_KB");
-        return e ? atoi(e) : 0;
-    }();
-    if (kb <= 0) return 0;
-    hipFuncAttributes a;
-    if (hipFuncGetAttributes(&a, fn) != hipSuccess) return 0;
-    const size_t want = (size_t)std::min(kb, 160) * 1024;
-    return want > a.sharedSizeBytes ? want - a.sharedSizeBytes : 0;
-}
-
-// Canonical totals (ora_csum level 2) of the m chunk trees cs[q][0..m) of K sums, by wave 0:
-// lane c holds chunk c and the K trees run packed (the same pairing as local_csum_inplace).
-// K = 28 is split over waves 0-3, 7 trees each (every value's packed tree is the canonical one
-// whatever the packing width, so the split changes no bit; wave 0 alone was a serial segment of
-// every LM trial).
-template <int K>
-__device__ __forceinline__ void pose_chunk_totals(double (*cs)[kPoseMaxEdges / 64], int m, double* res) {
-    constexpr int KW = K == 28 ? 7 : K;
-    const int w = threadIdx.x >> 6;
-    if (w >= K / KW) return;
-    const int lane = threadIdx.x & 63, q0 = w * KW;
-    if (m <= 1) {
-        if (lane < KW) res[q0 + lane] = m == 1 ? cs[q0 + lane][0] : 0.0;
-    } else if (m <= 64) {
-        double v[KW];
-#pragma unroll
-        for (int q = 0; q < KW; q++) v[q] = lane < m ? cs[q0 + q][lane] : 0.0;
-        const double t = packed_trees<KW>(v);
-        const int q = bitrev6(lane);
-        if (q < KW) res[q0 + q] = t;
-    } else if (lane < KW) {
-        res[q0 + lane] = local_csum_inplace(cs[q0 + lane], m);
-    }
-}
-
-// Block-wide canonical sums (ora_csum) of K per-active-edge values: wave w owns chunks
-// c = w, w + nw, ... of 64 active edges; the edge of chunk c + nw is loaded while chunk c is
-// computed.  f(e, i, out[K]) evaluates active edge i (edge e loaded).  Chunk trees go to
-// cs[q][c]; thread q < K finishes entry q.
-template <int K, class F, class Post>
-// post: run by thread 0 right after its own totals (res[0] among them) and before the closing
-// barrier, i.e. beside the other waves' totals
-__device__ __forceinline__ void pose_pass_post(F f, int nA, const uint16_t* aE, const PoseEdgeDev* E, double dM,
-                                               double dS, double (*cs)[kPoseMaxEdges / 64], double* res,
-                                               const PoseEdgeD& mine, int mineIdx, Post post) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, nw = blockDim.x >> 6;
-    const int m = (nA + 63) >> 6;
-    // chunk c = w is active edge tid: this thread's for the whole round, kept in registers
-    // (loaded once per round); later chunks are loaded one ahead.  One code path for every
-    // chunk count keeps a single inlined copy of f per call site (instruction-cache footprint)
-    int c = w;
-    int a = threadIdx.x;
-    int i = mineIdx;
-    PoseEdgeD e = mine;
-    while (c < m) {
-        const int cn = c + nw, an = cn * 64 + lane;
-        int in = 0;
-        PoseEdgeD en = e;
-        if (cn < m) {   // prefetch the next chunk's edge
-            in = an < nA ? aE[an] : 0;
-            en = pose_edge_load(E, in, dM, dS);
-        }
-        double v[K];
-        if (a < nA) f(e, i, v);
-        else
-#pragma unroll
-            for (int q = 0; q < K; q++) v[q] = 0.0;
-        if (nA == 1) {   // ora_csum keeps a single term untouched
-            if (lane == 0)
-#pragma unroll
-                for (int q = 0; q < K; q++) cs[q][0] = v[q];
-        } else {
-            const double t = packed_trees<K>(v);
-            const int q = bitrev6(lane);
-            if (q < K) cs[q][c] = t;
-        }
-        c = cn;
-        a = an;
-        i = in;
-        e = en;
-    }
-    __syncthreads();
-    pose_chunk_totals<K>(cs, nA > 0 ? m : 0, res);
-    if (threadIdx.x == 0) post();
-    __syncthreads();
-}
-template <int K, class F>
-__device__ __forceinline__ void pose_pass(F f, int nA, const uint16_t* aE, const PoseEdgeDev* E, double dM, double dS,
-                                          double (*cs)[kPoseMaxEdges / 64], double* res, const PoseEdgeD& mine,
-                                          int mineIdx) {
-    pose_pass_post<K>(f, nA, aE, E, dM, dS, cs, res, mine, mineIdx, [] {});
-}
-
-
-// ---- wave-level dense solve of the pose system ---------------------------------------
-__device__ __forceinline__ double lane_bcast(double v, int l) {
-    const unsigned long long u = __double_as_longlong(v);
-    const unsigned lo = __builtin_amdgcn_readlane((unsigned)(u & 0xffffffffu), l);
-    const unsigned hi = __builtin_amdgcn_readlane((unsigned)(u >> 32), l);
-    return __longlong_as_double(((unsigned long long)hi << 32) | lo);
-}
-// N independent IEEE divisions num[j] / den[j] as ONE lane-parallel division (lane j), results
-// broadcast to every lane.  The whole wave must be active and hold the same operands.
-template <int N>
-__device__ __forceinline__ void lane_div(const double* num, const double* den, double* out) {
-    const int lane = threadIdx.x & 63;
-    double a = num[0], b = den[0];
-#pragma unroll
-    for (int j = 1; j < N; j++) {
-        // opaque operands: a select chain over an array indexed by the lane otherwise becomes
-        // a scratch-memory lookup
-        double nj = num[j], dj = den[j];
-        asm volatile("" : "+v"(nj), "+v"(dj));
-        a = lane == j ? nj : a;
-        b = lane == j ? dj : b;
-    }
-    const double q = a / b;
-#pragma unroll
-    for (int j = 0; j < N; j++) out[j] = lane_bcast(q, j);
-}
-
-// LinearSolverDense (Eigen LDLT with diagonal pivoting) of (H + lambda I) x = b, H the packed
-// upper triangle Hs[21], run redundantly by a whole wave: the same IEEE operations as
-// ldlt_pivot6.  Left-looking LDLT never touches a diagonal entry before its own step, so the
-// pivot sequence is a function of |diag(H) + lambda| alone: it is fixed first, the
-// factorisation then runs unpivoted on P A P^T with static register indices, and the row
-// divisions of a step (and the 6 of the solve) are one lane-parallel division each.
-__device__ __forceinline__ bool pose_solve_w(const double* Hs, const double* bs, double lambda, double* x) {
-    // With distinct |pivots| the sequence is the descending order of |diag| (ties or NaN take
-    // the reference routine: its tie-break follows the swap history).  Ranks instead of swaps
-    // keep every index static (no scratch).
-    double dv[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) dv[i] = fabs(Hs[DIAG21[i]] + lambda);
-    bool distinct = true;
-    int rank[6];
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        int r = 0;
-        distinct = distinct && dv[j] == dv[j];
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-            if (i != j) {
-                r += dv[i] > dv[j] ? 1 : 0;
-                distinct = distinct && dv[i] != dv[j];
-            }
-        rank[j] = r;
-    }
-    int ord[6];
-#pragma unroll
-    for (int r = 0; r < 6; r++) {
-        int o = 0;
-#pragma unroll
-        for (int j = 0; j < 6; j++) o = rank[j] == r ? j : o;
-        ord[r] = o;
-    }
-    double A[36];   // lower triangle of P (H + lambda I) P^T
-#pragma unroll
-    for (int r = 0; r < 6; r++)
-#pragma unroll
-        for (int c = 0; c <= r; c++) {
-            const int a = min(ord[r], ord[c]), b = max(ord[r], ord[c]);
-            double h = Hs[a * 6 - (a * (a - 1)) / 2 + (b - a)];
-            if (r == c) h += lambda;
-            A[r * 6 + c] = h;
-        }
-    if (!distinct || !(fabs(A[0]) > 0.0)) {   // ties / NaN, or the reference's zero-pivot stop
-        double Hd[36], bb[6];
-#pragma unroll
-        for (int r = 0, q = 0; r < 6; r++)
-#pragma unroll
-            for (int cc = r; cc < 6; cc++, q++) {
-                double h = Hs[q];
-                if (cc == r) h += lambda;
-                Hd[r * 6 + cc] = h;
-                Hd[cc * 6 + r] = h;
-            }
-#pragma unroll
-        for (int j = 0; j < 6; j++) bb[j] = bs[j];
-        return ldlt_pivot6(Hd, bb, x);
-    }
-    int sign = 0;
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-        if (k > 0) {
-            double tmp[6];
-#pragma unroll
-            for (int j = 0; j < k; j++) tmp[j] = A[j * 6 + j] * A[k * 6 + j];
-            double s = 0;
-#pragma unroll
-            for (int j = 0; j < k; j++) s += A[k * 6 + j] * tmp[j];
-            A[k * 6 + k] -= s;
-#pragma unroll
-            for (int i = k + 1; i < 6; i++) {
-                double t = 0;
-#pragma unroll
-                for (int j = 0; j < k; j++) t += A[i * 6 + j] * tmp[j];
-                A[i * 6 + k] -= t;
-            }
-        }
-        const double akk = A[k * 6 + k];
-        if (k < 5 && fabs(akk) > 0.0) {
-            double num[5], den[5], q[5];
-#pragma unroll
-            for (int j = 0; j < 5; j++) {
-                num[j] = k + 1 + j < 6 ? A[(k + 1 + j) * 6 + k] : 1.0;
-                den[j] = akk;
-            }
-            lane_div<5>(num, den, q);
-#pragma unroll
-            for (int i = k + 1; i < 6; i++) A[i * 6 + k] = q[i - k - 1];
-        }
-        if (sign == 1) {
-            if (akk < 0) sign = 3;
-        } else if (sign == 2) {
-            if (akk > 0) sign = 3;
-        } else if (sign == 0) {
-            if (akk > 0) sign = 1;
-            else if (akk < 0) sign = 2;
-        }
-    }
-    if (!(sign == 1 || sign == 0)) return false;
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) y[i] = bs[ord[i]];
-#pragma unroll
-    for (int i = 0; i < 6; i++)
-#pragma unroll
-        for (int j = 0; j < i; j++) y[i] -= A[i * 6 + j] * y[j];
-    {
-        double den[6], q[6];
-#pragma unroll
-        for (int i = 0; i < 6; i++) den[i] = A[i * 6 + i];
-        lane_div<6>(y, den, q);
-#pragma unroll
-        for (int i = 0; i < 6; i++) y[i] = fabs(A[i * 6 + i]) > DBL_MIN ? q[i] : 0.0;
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; i--)
-#pragma unroll
-        for (int j = 5; j > i; j--) y[i] -= A[j * 6 + i] * y[j];
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        double v = 0.0;
-#pragma unroll
-        for (int p = 0; p < 6; p++)
-            if (ord[p] == j) v = y[p];
-        x[j] = v;
-    }
-    return true;
-}
-
-// The same solve with lane r holding row r of P (H + lambda I) P^T (lanes >= 6 shadow row 5):
-// every IEEE operation of pose_solve_w, each row's in the lane that owns it, so a step's row
-// updates and divisions are one lane-parallel instruction each and only the pivot and the
-// finished y_j travel between lanes; the backward sweep reads the columns of L through scr
-// (36 doubles of this wave's LDS).  x is returned in every lane.
-__device__ __forceinline__ bool pose_solve_l(const double* Hs, const double* bs, double lambda, double* x,
-                                             double* scr) {
-    double dv[6];
-#pragma unroll
-    for (int i = 0; i < 6; i++) dv[i] = fabs(Hs[DIAG21[i]] + lambda);
-    bool distinct = true;
-    int rank[6];
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        int r = 0;
-        distinct = distinct && dv[j] == dv[j];
-#pragma unroll
-        for (int i = 0; i < 6; i++)
-            if (i != j) {
-                r += dv[i] > dv[j] ? 1 : 0;
-                distinct = distinct && dv[i] != dv[j];
-            }
-        rank[j] = r;
-    }
-    int ord[6];
-#pragma unroll
-    for (int r = 0; r < 6; r++) {
-        int o = 0;
-#pragma unroll
-        for (int j = 0; j < 6; j++) o = rank[j] == r ? j : o;
-        ord[r] = o;
-    }
-    const double a00 = Hs[DIAG21[ord[0]]] + lambda;
-    if (!distinct || !(fabs(a00) > 0.0)) {   // ties / NaN, or the reference's zero-pivot stop
-        double Hd[36], bb[6];
-#pragma unroll
-        for (int r = 0, q = 0; r < 6; r++)
-#pragma unroll
-            for (int cc = r; cc < 6; cc++, q++) {
-                double h = Hs[q];
-                if (cc == r) h += lambda;
-                Hd[r * 6 + cc] = h;
-                Hd[cc * 6 + r] = h;
-            }
-#pragma unroll
-        for (int j = 0; j < 6; j++) bb[j] = bs[j];
-        return ldlt_pivot6(Hd, bb, x);
-    }
-    const int lane = threadIdx.x & 63, row = lane < 6 ? lane : 5;
-    int orow = ord[0];
-#pragma unroll
-    for (int p = 1; p < 6; p++) orow = row == p ? ord[p] : orow;
-    double a[6];   // row `row` of P (H + lambda I) P^T, lower part used
-#pragma unroll
-    for (int c = 0; c < 6; c++) {
-        const int i0 = min(orow, ord[c]), i1 = max(orow, ord[c]);
-        double h = Hs[i0 * 6 - (i0 * (i0 - 1)) / 2 + (i1 - i0)];
-        if (row == c) h += lambda;
-        a[c] = h;
-    }
-    // branch-free: the reference's sign state machine ends in 1 / 2 / 3 / 0 exactly when some /
-    // only positive, only negative, both, no nonzero pivots were seen, so two flags replace it
-    double d[6];
-    bool anyNeg = false;
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-        if (k > 0) {
-            double tmp[6];
-#pragma unroll
-            for (int j = 0; j < k; j++) tmp[j] = d[j] * lane_bcast(a[j], k);   // A[j][j] * A[k][j]
-            double u = 0;
-#pragma unroll
-            for (int j = 0; j < k; j++) u += a[j] * tmp[j];
-            const double ak = a[k] - u;
-            a[k] = row >= k ? ak : a[k];
-        }
-        const double akk = lane_bcast(a[k], k);
-        d[k] = akk;
-        if (k < 5) {
-            const double q = a[k] / akk;
-            a[k] = (fabs(akk) > 0.0 && row > k) ? q : a[k];
-        }
-        anyNeg = anyNeg || akk < 0;
-    }
-    if (anyNeg) return false;
-    double y = bs[orow];
-#pragma unroll
-    for (int j = 0; j < 5; j++) {
-        const double yj = lane_bcast(y, j);
-        const double v = y - a[j] * yj;
-        y = row > j ? v : y;
-    }
-    double arr = a[0];
-#pragma unroll
-    for (int c = 1; c < 6; c++) arr = row == c ? a[c] : arr;   // own diagonal
-    {
-        const double q = y / arr;
-        y = fabs(arr) > DBL_MIN ? q : 0.0;
-    }
-    // columns of L: lane r needs A[j][r], j > r
-    if (lane < 6)
-#pragma unroll
-        for (int c = 0; c < 6; c++) scr[lane * 6 + c] = a[c];
-    __builtin_amdgcn_s_waitcnt(0xc07f);   // lgkmcnt(0)
-    __builtin_amdgcn_wave_barrier();
-    double col[6];
-#pragma unroll
-    for (int j = 0; j < 6; j++) col[j] = scr[j * 6 + row];
-#pragma unroll
-    for (int j = 5; j >= 1; j--) {
-        const double xj = lane_bcast(y, j);
-        const double v = y - col[j] * xj;
-        y = row < j ? v : y;
-    }
-    double yb[6];
-#pragma unroll
-    for (int p = 0; p < 6; p++) yb[p] = lane_bcast(y, p);
-#pragma unroll
-    for (int j = 0; j < 6; j++) {
-        double v = 0.0;
-#pragma unroll
-        for (int p = 0; p < 6; p++)
-            if (ord[p] == j) v = yb[p];
-        x[j] = v;
-    }
-    return true;
-}
-
-template <int NT>
-__global__ void __launch_bounds__(NT) k_pose_opt(PoseProbDev* probs, const PoseEdgeDev* __restrict__ Eall,
-                                                 double* errAll, uint8_t* outlAll) {
-    ORBGPU_LATENCY_WAVE();
-    constexpr int kPosePer = kPoseMaxEdges / NT;
-    PoseProbDev& P = probs[blockIdx.x];
-    const int ne = P.ne;
-    const PoseEdgeDev* E = Eall + P.e0;
-    (void)errAll;   // errors are recomputed at classification instead of kept per pass
-    uint8_t* outl = outlAll + P.e0;
-    // LDS kept near 53 KiB so three workgroups fit a CU next to the extraction kernels: edge
-    // flags (bit 0: level 1 = inactive, bit 1: robust kernel set), active-edge list as u16
-    __shared__ uint8_t fl[kPoseMaxEdges];
-    __shared__ uint16_t aE[kPoseMaxEdges];
-    __shared__ double cs[28][kPoseMaxEdges / 64];
-    __shared__ double red[32];
-    // speculative solves for 1..kPoseSpec consecutive rejections of a trial (waves 1..kPoseSpec)
-    constexpr int kPoseSpec = 3;
-    __shared__ Se3 T, Terr, Tbase, Tc[kPoseSpec + 1];   // Tc: the candidates of a round of trials
-    __shared__ double xc[kPoseSpec + 1][6];
-    __shared__ int okc[kPoseSpec + 1];
-    __shared__ double scrSolve[kPoseSpec + 1][36];   // pose_solve_l's column exchange, one per solving wave
-    __shared__ double xs[6], Hs[21], bs[6], sysN[28];
-    __shared__ double lambda, ni, currentChi, iniChi;
-    __shared__ int nA, nBadLM, qmax, again, term, nBad, haveSys, specPass, wsum[16];
-    const int tid = threadIdx.x;
-    const double dM = (double)(float)sqrt(5.991), dS = (double)(float)sqrt(7.815);
-    if (ne < 0) {   // device mode: capacity exceeded (reported by the host)
-        if (tid == 0 && P.ninl) *P.ninl = -1;
-        return;
-    }
-    if (ne < 3) {
-        if (tid == 0) {
-            P.T = P.T0;
-            P.nbad = -1;
-            if (P.ninl) *P.ninl = 0;
-        }
-        if (P.Tcw_out) {
-            if (tid < 16) P.Tcw_out[tid] = P.Tcw[tid];
-            for (int i = tid; i < ne; i += blockDim.x) P.outlier[E[i].meta & 0x7fffffff] = 0;
-            // Tcw_out may be pinned host memory read by a host that polls a later kernel's signal
-            // word: write the pose back at system scope before this workgroup ends
-            if (tid < 16) __threadfence_system();
-        }
-        return;
-    }
-    for (int i = tid; i < ne; i += blockDim.x) {
-        fl[i] = 2;
-        outl[i] = 0;
-    }
-    __syncthreads();
-    const float chi2Mono = 5.991f, chi2Stereo = 7.815f;
-    for (int it = 0; it < 4; it++) {
-        if (tid == 0) {
-            T = P.T0;   // vSE3->setEstimate(Converter::toSE3Quat(pFrame->mTcw)) every round
-            for (int j = 0; j < 6; j++) xs[j] = 0.0;
-        }
-        // active edges (level 0) in edge order: block prefix over kPosePer edges per thread
-        {
-            const int base = tid * kPosePer;
-            int c = 0;
-            for (int j = 0; j < kPosePer; j++) c += (base + j < ne && (fl[base + j] & 1) == 0) ? 1 : 0;
-            int incl = c;   // inclusive scan within the wave
-            for (int o = 1; o < 64; o <<= 1) {
-                const int t = __shfl_up(incl, o, 64);
-                if ((tid & 63) >= o) incl += t;
-            }
-            if ((tid & 63) == 63) wsum[tid >> 6] = incl;
-            __syncthreads();
-            int off = 0;
-            for (int w = 0; w < (tid >> 6); w++) off += wsum[w];
-            int pos = off + incl - c;
-            for (int j = 0; j < kPosePer; j++)
-                if (base + j < ne && (fl[base + j] & 1) == 0) aE[pos++] = (uint16_t)(base + j);
-            if (tid == blockDim.x - 1) nA = off + incl;
-            __syncthreads();
-        }
-        const int na = nA;
-        const int myIdx = tid < na ? aE[tid] : 0;
-        const PoseEdgeD myE = pose_edge_load(E, myIdx, dM, dS);
-        if (na > 0) {   // optimize(10); without active edges the vertex is not optimised at all
-            ORBGPU_PROF_START;
-            // J, robust weight and the 28 entries (robust chi2, J^T W J upper triangle, -J^T W e)
-            // of active edge i at pose X, into v[0..28)
-            auto sys_terms = [&](const PoseEdgeD& e, int i, const Se3& X, double* v) {
-                double p[3];
-                se3_map(X, e.X, p);
-                const SharedDiv dz(p[2]);
-                double e3[3];
-                pose_err_p(e, p, dz, P, e3);
-                const double c = pose_chi2(e, e3);
-                const bool rb = (fl[i] & 2) != 0;
-                v[0] = pose_rho0(e, c, rb);
-                const double x = p[0], y = p[1], invz = dz.div(1.0), invz_2 = invz * invz;
-                double J[18];
-                J[0] = ((x * y) * invz_2) * P.fx;
-                J[1] = (-(1 + ((x * x) * invz_2))) * P.fx;
-                J[2] = (y * invz) * P.fx;
-                J[3] = (-invz) * P.fx;
-                J[4] = 0;
-                J[5] = (x * invz_2) * P.fx;
-                J[6] = (1 + ((y * y) * invz_2)) * P.fy;
-                J[7] = (((-x) * y) * invz_2) * P.fy;
-                J[8] = ((-x) * invz) * P.fy;
-                J[9] = 0;
-                J[10] = (-invz) * P.fy;
-                J[11] = (y * invz_2) * P.fy;
-                J[12] = J[0] - ((P.bf * y) * invz_2);
-                J[13] = J[1] + ((P.bf * x) * invz_2);
-                J[14] = J[2];
-                J[15] = J[3];
-                J[16] = 0;
-                J[17] = J[5] - (P.bf * invz_2);
-                // monocular edges: a zero third Jacobian row (and err[2] = 0) makes every
-                // third term +-0, an exact identity on the two-term partial sums (which
-                // start from +0 + t0 and so are never -0): the sums run branch-free
-#pragma unroll
-                for (int j = 12; j < 18; j++) J[j] = e.stereo ? J[j] : 0.0;
-                double r1 = 1.;
-                if (rb && !(c <= e.dsqr)) r1 = e.delta / sqrt(c);
-                const double wgt = rb ? r1 * e.info : e.info;
-                double omr[3];
-#pragma unroll
-                for (int kk = 0; kk < 3; kk++) {
-                    omr[kk] = -(e.info * e3[kk]);
-                    if (rb) omr[kk] *= r1;
-                }
-#pragma unroll
-                for (int r = 0; r < 6; r++) {
-                    double sb = 0;
-#pragma unroll
-                    for (int kk = 0; kk < 3; kk++) sb += J[kk * 6 + r] * omr[kk];
-                    v[22 + r] = sb;
-#pragma unroll
-                    for (int cc = r; cc < 6; cc++) {
-                        double hh = 0;
-#pragma unroll
-                        for (int kk = 0; kk < 3; kk++) hh += (J[kk * 6 + r] * wgt) * J[kk * 6 + cc];
-                        v[1 + r * 6 - (r * (r - 1)) / 2 + (cc - r)] = hh;
-                    }
-                }
-            };
-            // One LM iteration is a system pass at T (skipped when the accepted trial of the
-            // previous iteration already evaluated it) followed by trials; a trial is the solves
-            // (waves 0..kPoseSpec) and ONE pass at candidate 0.  Both passes run through the same
-            // call site (sysPhase picks the pose), and the four solves through one: a single
-            // inlined copy of the 28-sum edge body keeps the LM loop's code within the
-            // instruction cache the workgroup shares with its neighbours.
-            if (tid == 0) haveSys = 0;
-            __syncthreads();
-            int kit = 0;            // LM iteration (uniform: every thread steps it alike)
-            bool sysPhase = true;   // the next pass evaluates the system at T
-            for (;;) {
-                if (!sysPhase) {
-                    ORBGPU_PROF_MARK(10);
-                    // Trials, up to four per round: candidate 0 solves at the current lambda
-                    // (wave 0) while waves 1..kPoseSpec solve the systems of 1..kPoseSpec
-                    // consecutive rejections (lambda *= ni; ni *= 2, the same H, b and starting
-                    // estimate).  The pass of the first trial computes the whole system at
-                    // candidate 0 (its robust chi2 is entry 0), so an accepted first trial hands
-                    // the next iteration its system; a rejected one is followed by ONE pass for
-                    // the speculative candidates, whose trials are then replayed in the
-                    // reference's order.
-                    if (tid < 64 * (kPoseSpec + 1)) {
-                        const int L = tid >> 6;   // 0: the current trial, L: L rejections ahead
-                        double ls = lambda, ns = ni;
-                        for (int j = 0; j < L; j++) {
-                            ls *= ns;
-                            ns *= 2;
-                        }
-                        double xn[6];
-#ifndef ORBGPU_POSE_SOLVE_W
-                        const bool ok = pose_solve_l(Hs, bs, ls, xn, scrSolve[L]);
-#else
-                        const bool ok = pose_solve_w(Hs, bs, ls, xn);
-#endif
-                        ORBGPU_PROF_MARK(5);
-                        ORBGPU_PROF_COUNT(9);
-                        // candidate 0 steps from xs when the solve fails (its trial is then
-                        // rejected: tempChi = DBL_MAX); a failed speculative solve stays at Tbase
-                        double xl[6];
-#pragma unroll
-                        for (int j = 0; j < 6; j++) xl[j] = (ok || L > 0) ? xn[j] : xs[j];
-                        Se3 r = Tbase;
-                        if (ok || L == 0) {
-                            Se3 d;
-                            se3_exp(xl, d);
-                            se3_mul(d, Tbase, r);
-                        }
-                        if ((tid & 63) == 0) {
-                            Tc[L] = r;
-#pragma unroll
-                            for (int j = 0; j < 6; j++) xc[L][j] = xl[j];
-                            okc[L] = ok ? 1 : 0;
-                        }
-                    }
-                    __syncthreads();
-                    ORBGPU_PROF_MARK(2);
-                } else {
-                    ORBGPU_PROF_MARK(0);
-                    ORBGPU_PROF_COUNT(8);
-                }
-                // one trial of the reference's loop (optimization_algorithm_levenberg.cpp:100-149)
-                // at candidate j with robust chi2 tempChi; tid 0 only
-                auto trial = [&](int j, double tempChi) {
-                    if (!okc[j]) tempChi = DBL_MAX;
-#pragma unroll
-                    for (int q = 0; q < 6; q++) xs[q] = xc[j][q];
-                    double rho = currentChi - tempChi;
-                    double sv[6];
-                    for (int q = 0; q < 6; q++) sv[q] = xs[q] * (lambda * xs[q] + bs[q]);
-                    double scale = tree64_local([&](int q) { return sv[q]; }, 6);
-                    scale += 1e-3;
-                    rho /= scale;
-                    Terr = Tc[j];   // the pose of the last computeActiveErrors
-                    if (rho > 0 && isfinite(tempChi)) {
-                        const double a3 = 2 * rho - 1;
-                        double alpha = 1. - (a3 * a3) * a3;
-                        alpha = fmin(alpha, 2. / 3.);
-                        const double scaleFactor = fmax(1. / 3., alpha);
-                        lambda *= scaleFactor;
-                        ni = 2;
-                        currentChi = tempChi;
-                        T = Tc[j];
-                        if (j == 0) haveSys = 1;   // red[0..28) is the system at the new estimate
-                    } else {
-                        lambda *= ni;
-                        ni *= 2;
-                        T = Tbase;
-                    }
-                    qmax++;
-                    again = (rho < 0 && qmax < 10) ? 1 : 0;
-                    if (!again) {
-                        if (qmax == 10 || rho == 0) {
-                            term = 1;
-                        } else {
-                            if ((iniChi - currentChi) * 1e3 < iniChi) nBadLM++;
-                            else nBadLM = 0;
-                            term = nBadLM >= 3 ? 1 : 0;
-                        }
-                    }
-                };
-                // sysPhase: computeActiveErrors + activeRobustChi2 (entry 0) and buildSystem
-                // (entries 1..27) at T; a trial: its robust chi2 at candidate 0 and, with it, the
-                // system at that estimate (the next iteration's whenever the trial is accepted).
-                // Canonical sums per entry.
-                {   // a trial's decision runs on thread 0 as soon as its chi2 total (red[0]) is in,
-                    // beside the other waves' totals (the pass reads no state the decision writes)
-                    const Se3& X = sysPhase ? T : Tc[0];
-                    pose_pass_post<28>([&](const PoseEdgeD& e, int i, double* v) { sys_terms(e, i, X, v); }, na, aE, E,
-                                       dM, dS, cs, red, myE, myIdx, [&] {
-                                           if (!sysPhase) {
-                                               trial(0, red[0]);
-                                               specPass = again && okc[1] ? 1 : 0;
-                                           }
-                                       });
-                }
-                if (sysPhase) {
-                    ORBGPU_PROF_MARK(1);
-                    if (tid < 28) {
-                        if (tid == 0) currentChi = iniChi = red[0];
-                        else if (tid < 22) Hs[tid - 1] = red[tid];
-                        else bs[tid - 22] = red[tid];
-                    }
-                } else {
-                    ORBGPU_PROF_MARK(3);
-                    if (haveSys && tid < 28) sysN[tid] = red[tid];
-                    if (specPass) {
-                        // candidate 0 rejected: the speculative candidates' robust chi2 in one pass,
-                        // then their trials in order while they are rejected
-                        pose_pass<kPoseSpec>([&](const PoseEdgeD& e, int i, double* v) {
-#pragma unroll
-                            for (int L = 1; L <= kPoseSpec; L++) {
-                                double e3[3];
-                                pose_err(e, Tc[L], P, e3);
-                                v[L - 1] = pose_rho0(e, pose_chi2(e, e3), (fl[i] & 2) != 0);
-                            }
-                        }, na, aE, E, dM, dS, cs, red, myE, myIdx);
-                        if (tid == 0)
-                            for (int j = 1; j <= kPoseSpec && again && okc[j]; j++) trial(j, red[j - 1]);
-                        __syncthreads();
-                    }
-                    ORBGPU_PROF_MARK(4);
-                    if (again) continue;   // the next trial of this iteration
-                    __syncthreads();
-                    if (term || ++kit == 10) break;
-                    if (!haveSys) {   // the next iteration starts with a system pass at T
-                        sysPhase = true;
-                        continue;
-                    }
-                    if (tid < 28) {   // the system at this estimate came with its accepted trial
-                        if (tid == 0) currentChi = iniChi = sysN[0];
-                        else if (tid < 22) Hs[tid - 1] = sysN[tid];
-                        else bs[tid - 22] = sysN[tid];
-                    }
-                }
-                // iteration start (Hs, bs, currentChi = iniChi are the system at T)
-                __syncthreads();
-                if (tid == 0) {
-                    if (kit == 0) {   // computeLambdaInit over the pose diagonal
-                        double mx = 0.;
-                        for (int j = 0; j < 6; j++) mx = fmax(fabs(Hs[DIAG21[j]]), mx);
-                        lambda = 1e-5 * mx;
-                        ni = 2;
-                        nBadLM = 0;
-                    }
-                    qmax = 0;
-                    haveSys = 0;
-                    Tbase = T;   // the estimate every trial of this iteration starts from
-                }
-                sysPhase = false;
-                __syncthreads();
-            }
-        }
-        // classification (Optimizer.cc:376-426): outliers get their error recomputed
-        if (tid == 0) nBad = 0;
-        __syncthreads();
-        int mybad = 0;
-        for (int i = tid; i < ne; i += blockDim.x) {
-            const PoseEdgeD e = pose_edge_load(E, i, dM, dS);
-            // active edges keep the error of the last pass (recomputed: the same operations on
-            // the same pose), outliers get computeError() at the final estimate
-            double e3[3];
-            pose_err(e, outl[i] ? T : Terr, P, e3);
-            const float chi2 = (float)pose_chi2(e, e3);
-            uint8_t f = fl[i];
-            if (chi2 > (e.stereo ? chi2Stereo : chi2Mono)) {
-                outl[i] = 1;
-                f |= 1;
-                mybad++;
-            } else {
-                outl[i] = 0;
-                f &= 2;
-            }
-            if (it == 2) f &= 1;   // setRobustKernel(0)
-            fl[i] = f;
-        }
-        if (mybad) atomicAdd(&nBad, mybad);
-        __syncthreads();
-        if (ne < 10) break;   // optimizer.edges().size() < 10
-    }
-    if (tid == 0) {
-        P.T = T;
-        P.nbad = nBad;
-        if (P.ninl) *P.ninl = ne - nBad;
-    }
-    if (P.Tcw_out) {   // pFrame->SetPose(Converter::toCvMat(SE3quat_recov)); mvbOutlier
-        if (tid == 0) {
-            double R[9];
-            quat_to_R(T.q, R);
-            float* o = P.Tcw_out;
-            for (int r = 0; r < 3; r++) {
-                for (int c = 0; c < 3; c++) o[r * 4 + c] = (float)R[r * 3 + c];
-                o[r * 4 + 3] = (float)T.t[r];
-            }
-            o[12] = o[13] = o[14] = 0.f;
-            o[15] = 1.f;
-            __threadfence_system();   // see the ne < 3 exit above: host-visible before the workgroup ends
-        }
-        for (int i = tid; i < ne; i += blockDim.x) P.outlier[E[i].meta & 0x7fffffff] = outl[i];
-    }
-}
-
-// Device mode edge creation (Optimizer.cc:268-347): rows with a map point, keypoint order,
-// compacted by a block scan; the initial pose from the frame's Tcw.  One workgroup per frame.
-// 4 waves: the pack fits in the slot of one retiring extraction workgroup
-constexpr int kPackThreads = 256;
-__global__ void __launch_bounds__(kPackThreads) k_pose_pack(PoseProbDev* probs, PoseEdgeDev* Eall) {
-    ORBGPU_LATENCY_WAVE();
-    PoseProbDev& P = probs[blockIdx.x];
-    const int N = P.N, tid = threadIdx.x;
-    PoseEdgeDev* E = Eall + P.e0;
-    __shared__ int wsum[kPackThreads / 64], base;
-    if (tid == 0) {
-        base = 0;
-        double R[9];
-        for (int r = 0; r < 3; r++)
-            for (int c = 0; c < 3; c++) R[r * 3 + c] = (double)P.Tcw[r * 4 + c];
-        quat_from_R(R, P.T0.q);
-        for (int r = 0; r < 3; r++) P.T0.t[r] = (double)P.Tcw[r * 4 + 3];
-        P.T0.pad = 0;
-        se3_normalize(P.T0);
-    }
-    __syncthreads();
-    for (int c0 = 0; c0 < N; c0 += kPackThreads) {
-        const int i = c0 + tid;
-        const int f = i < N ? (P.mpidx ? (P.mpidx[i] >= 0 ? 1 : 0) : (P.has_mp[i] ? 1 : 0)) : 0;
-        int incl = f;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(incl, o, 64);
-            if ((tid & 63) >= o) incl += t;
-        }
-        if ((tid & 63) == 63) wsum[tid >> 6] = incl;
-        __syncthreads();
-        int off = base;
-        for (int w = 0; w < (tid >> 6); w++) off += wsum[w];
-        if (f) {
-            const int k = off + incl - 1;
-            if (k < kPoseMaxEdges) {
-                PoseEdgeDev e;
-                if (P.mpidx) {
-                    // Optimizer.cc:268-347: pMP->GetWorldPos(), kpUn.pt, mvuRight, mvInvLevelSigma2[kpUn.octave]
-                    const size_t m = (size_t)P.mpidx[i];
-                    for (int j = 0; j < 3; j++) e.Xw[j] = P.mp_pos[3 * m + j];
-                    e.obs[0] = P.keys[7 * (size_t)i];
-                    e.obs[1] = P.keys[7 * (size_t)i + 1];
-                    e.obs[2] = P.uR[i];
-                    const int oct = min(max(__float_as_int(P.keys[7 * (size_t)i + 5]), 0), P.nlev - 1);
-                    e.info = P.isig_tab[oct];
-                } else {
-                    for (int j = 0; j < 3; j++) {
-                        e.Xw[j] = P.Xw[3 * i + j];
-                        e.obs[j] = P.obs[3 * i + j];
-                    }
-                    e.info = P.inv_sigma2[i];
-                }
-                e.meta = i | (!(e.obs[2] < 0) ? (int)0x80000000u : 0);
-                E[k] = e;
-            }
-        }
-        __syncthreads();
-        if (tid == kPackThreads - 1) base = off + incl;
-        __syncthreads();
-    }
-    if (tid == 0) P.ne = base > kPoseMaxEdges ? -1 : base;
-}
-
-// ---------------------------------------------------------------- host
-static void host_se3_from_Tcw(const float* T, Se3& o) {
-    double R[9];
-    for (int r = 0; r < 3; r++)
-        for (int c = 0; c < 3; c++) R[r * 3 + c] = (double)T[r * 4 + c];
-    quat_from_R(R, o.q);
-    for (int r = 0; r < 3; r++) o.t[r] = (double)T[r * 4 + 3];
-    o.pad = 0;
-    se3_normalize(o);
-}
-
-static void host_se3_to_Tcw(const Se3& s, float* T) {
-    double R[9];
-    quat_to_R(s.q, R);
-    for (int r = 0; r < 3; r++) {
-        for (int c = 0; c < 3; c++) T[r * 4 + c] = (float)R[r * 3 + c];
-        T[r * 4 + 3] = (float)s.t[r];
-    }
-    T[12] = T[13] = T[14] = 0.f;
-    T[15] = 1.f;
-}
-
-// ---------------------------------------------------------------- PoseEngine
-int PoseEngine::run_device(int count, const pose_problem* P, float* const* Tcw_out, uint8_t* const* outlier,
-                           int* ninliers) {
-    std::vector<int> Ns(count);
-    for (int f = 0; f < count; f++) Ns[f] = P[f].N;
-    return launch_device(count, Ns.data(), [&](int f, PoseProbDev& pp) {
-        const pose_problem& Q = P[f];
-        pp.fx = Q.fx; pp.fy = Q.fy; pp.cx = Q.cx; pp.cy = Q.cy; pp.bf = Q.bf;
-        pp.Tcw = Q.Tcw; pp.has_mp = Q.has_mp; pp.Xw = Q.Xw; pp.obs = Q.obs; pp.inv_sigma2 = Q.inv_sigma2;
-    }, Tcw_out, outlier, ninliers);
-}
-
-int PoseEngine::run_frames_device(int count, const pose_frame* F, float* const* Tcw_out, uint8_t* const* outlier,
-                                  int* ninliers, hipStream_t s, DeferredChain* chain) {
-    std::vector<int> Ns(count);
-    for (int f = 0; f < count; f++) Ns[f] = F[f].N;
-    return launch_device(count, Ns.data(), [&](int f, PoseProbDev& pp) {
-        const pose_frame& Q = F[f];
-        pp.fx = Q.fx; pp.fy = Q.fy; pp.cx = Q.cx; pp.cy = Q.cy; pp.bf = Q.bf;
-        pp.Tcw = Q.Tcw;
-        pp.mpidx = Q.mp; pp.mp_pos = Q.mp_pos; pp.keys = (const float*)Q.keysUn; pp.uR = Q.uRight;
-        pp.isig_tab = Q.invLevelSigma2; pp.nlev = Q.nlevels;
-    }, Tcw_out, outlier, ninliers, s, chain);
-}
-
-// Device-mode launch.  Default: own stream, results synchronised before return.  With a
-// DeferredChain: enqueued on `s` behind the caller's previous work, the problem table staged
-// through the chain's pinned blocks and the inlier counts landing in `ninliers` at
-// chain.finish() (-1 for a frame over kPoseMaxEdges).
-int PoseEngine::launch_device(int count, const int* Ns, const std::function<void(int, PoseProbDev&)>& fill,
-                              float* const* Tcw_out, uint8_t* const* outlier, int* ninliers, hipStream_t s,
-                              DeferredChain* chain) {
-    hipStream_t st = s ? s : stream_;
-    size_t nmax = 0;
-    for (int f = 0; f < count; f++) nmax += (size_t)std::min(Ns[f], kPoseMaxEdges + 1);
-    const auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t bProb = al(sizeof(PoseProbDev) * count), bEdge = al(sizeof(PoseEdgeDev) * std::max<size_t>(nmax, 1));
-    const size_t bOut = al(std::max<size_t>(nmax, 1)), bNin = al(sizeof(int) * count);
-    const size_t need = bProb + bEdge + bOut + bNin;
-    if (need > cap_) {
-        if (lastUseSet_) ORB_HIP_CHECK(hipEventSynchronize(lastUse_));   // queued kernels may still read it
-        if (dArena_) (void)hipFree(dArena_);
-        if (hArena_) (void)hipHostFree(hArena_);
-        dArena_ = hArena_ = nullptr;
-        cap_ = 0;
-        ORB_HIP_CHECK(hipMalloc(&dArena_, need));
-        ORB_HIP_CHECK(hipHostMalloc(&hArena_, need));
-        cap_ = need;
-    }
-    char* d = (char*)dArena_;
-    // inlier counts: the arena, or in a chain its count blocks (copied when the chain closes)
-    int* dNin = chain ? (int*)chain->dev_counts(sizeof(int) * count) : (int*)(d + bProb + bEdge + bOut);
-    if (!dNin) return -2;
-    std::vector<PoseProbDev> tmp;
-    PoseProbDev* hp = (PoseProbDev*)hArena_;
-    if (chain) {   // hArena_ may still be the source of an earlier queued copy: stage instead
-        tmp.resize(count);
-        hp = tmp.data();
-    }
-    size_t e0 = 0;
-    for (int f = 0; f < count; f++) {
-        PoseProbDev& pp = hp[f];
-        memset(&pp, 0, sizeof(pp));
-        pp.N = Ns[f];
-        pp.e0 = (int)e0;
-        e0 += (size_t)std::min(Ns[f], kPoseMaxEdges + 1);
-        fill(f, pp);
-        pp.Tcw_out = Tcw_out[f];
-        pp.outlier = outlier[f];
-        pp.ninl = dNin + f;
-    }
-    PoseProbDev* dp = (PoseProbDev*)d;
-    PoseEdgeDev* dE = (PoseEdgeDev*)(d + bProb);
-    const void* src = chain ? chain->stage(hp, sizeof(PoseProbDev) * count) : (const void*)hp;
-    if (!src) return -2;
-    // the arena's previous user may be queued on another stream (a deferred chain of another
-    // matcher, or this engine's own stream): overwrite the problem table only after it is done
-    if (lastUseSet_) ORB_HIP_CHECK(hipStreamWaitEvent(st, lastUse_, 0));
-    ORB_HIP_CHECK(hipMemcpyAsync(d, src, sizeof(PoseProbDev) * count, hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(k_pose_pack, dim3(count), dim3(kPackThreads), 0, st, dp, dE);
-    if (timing_) ORB_HIP_CHECK(hipEventRecord(tA_, st));
-    if (count <= pose_wide_max())
-        hipLaunchKernelGGL(k_pose_opt<kPoseThreadsWide>, dim3(count), dim3(kPoseThreadsWide),
-                           pose_lds_pad((const void*)k_pose_opt<kPoseThreadsWide>), st, dp, (const PoseEdgeDev*)dE,
-                           nullptr, (uint8_t*)(d + bProb + bEdge));
-    else
-        hipLaunchKernelGGL(k_pose_opt<kPoseThreads>, dim3(count), dim3(kPoseThreads),
-                           pose_lds_pad((const void*)k_pose_opt<kPoseThreads>), st, dp, (const PoseEdgeDev*)dE, nullptr,
-                           (uint8_t*)(d + bProb + bEdge));
-    ORB_HIP_CHECK(hipGetLastError());
-    if (timing_) {
-        ORB_HIP_CHECK(hipEventRecord(tB_, st));
-        timed_ = true;
-    }
-    if (chain) {
-        chain->land_dev(ninliers, dNin, sizeof(int) * count);
-        ORB_HIP_CHECK(hipEventRecord(lastUse_, st));
-        lastUseSet_ = true;
-        return 0;
-    }
-    ORB_HIP_CHECK(hipMemcpyAsync(hp, d, bProb, hipMemcpyDeviceToHost, st));
-    ORB_HIP_CHECK(hipEventRecord(lastUse_, st));
-    lastUseSet_ = true;
-    ORB_HIP_CHECK(stream_wait(st));
-    int rc = 0;
-    for (int f = 0; f < count; f++) {
-        const PoseProbDev& pp = hp[f];
-        if (pp.ne < 0) rc = -3;
-        ninliers[f] = pp.ne < 0 || pp.nbad < 0 ? 0 : pp.ne - pp.nbad;
-    }
-    return rc;
-}
-
-int PoseEngine::last_timing(float* ms) {
-    if (!timed_) return -1;
-    ORB_HIP_CHECK(hipEventSynchronize(tB_));
-    ORB_HIP_CHECK(hipEventElapsedTime(ms, tA_, tB_));
-    return 0;
-}
-
-PoseEngine::~PoseEngine() {
-    if (lastUseSet_) (void)hipEventSynchronize(lastUse_);
-    if (lastUse_) (void)hipEventDestroy(lastUse_);
-    if (tA_) (void)hipEventDestroy(tA_);
-    if (tB_) (void)hipEventDestroy(tB_);
-    if (dArena_) (void)hipFree(dArena_);
-    if (hArena_) (void)hipHostFree(hArena_);
-    if (stream_) (void)hipStreamDestroy(stream_);
-}
-
-int PoseEngine::init() {
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return -4;
-    ORB_HIP_CHECK(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
-    ORB_HIP_CHECK(hipEventCreateWithFlags(&lastUse_, hipEventDisableTiming));
-    ORB_HIP_CHECK(hipEventCreate(&tA_));
-    ORB_HIP_CHECK(hipEventCreate(&tB_));
-    return 0;
-}
-
-// Edge creation (Optimizer.cc:268-347): rows with a map point in keypoint order.
-int PoseEngine::run(int count, const pose_problem* P, float* Tcw_out, uint8_t* const* outlier, int* ninliers) {
-    size_t ne = 0;
-    std::vector<int> nE(count);
-    for (int f = 0; f < count; f++) {
-        int c = 0;
-        for (int i = 0; i < P[f].N; i++) c += P[f].has_mp[i] ? 1 : 0;
-        if (c > kPoseMaxEdges) return -3;
-        nE[f] = c;
-        ne += c;
-    }
-    const auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t bProb = al(sizeof(PoseProbDev) * count), bEdge = al(sizeof(PoseEdgeDev) * std::max<size_t>(ne, 1));
-    const size_t bErr = al(sizeof(double) * 3 * std::max<size_t>(ne, 1)), bOut = al(std::max<size_t>(ne, 1));
-    const size_t need = bProb + bEdge + bErr + bOut;
-    if (lastUseSet_) ORB_HIP_CHECK(hipEventSynchronize(lastUse_));   // hArena_ / dArena_ free again
-    if (need > cap_) {
-        if (dArena_) (void)hipFree(dArena_);
-        if (hArena_) (void)hipHostFree(hArena_);
-        dArena_ = hArena_ = nullptr;
-        cap_ = 0;
-        ORB_HIP_CHECK(hipMalloc(&dArena_, need));
-        ORB_HIP_CHECK(hipHostMalloc(&hArena_, need));
-        cap_ = need;
-    }
-    char* h = (char*)hArena_;
-    char* d = (char*)dArena_;
-    PoseProbDev* hp = (PoseProbDev*)h;
-    PoseEdgeDev* he = (PoseEdgeDev*)(h + bProb);
-    uint8_t* hOut = (uint8_t*)(h + bProb + bEdge + bErr);
-    int e0 = 0;
-    for (int f = 0; f < count; f++) {
-        const pose_problem& Q = P[f];
-        PoseProbDev& pp = hp[f];
-        memset(&pp, 0, sizeof(pp));
-        pp.ne = nE[f];
-        pp.e0 = e0;
-        host_se3_from_Tcw(Q.Tcw, pp.T0);
-        pp.fx = Q.fx; pp.fy = Q.fy; pp.cx = Q.cx; pp.cy = Q.cy; pp.bf = Q.bf;
-        for (int i = 0; i < Q.N; i++) {
-            if (!Q.has_mp[i]) continue;
-            PoseEdgeDev& e = he[e0++];
-            for (int j = 0; j < 3; j++) {
-                e.Xw[j] = Q.Xw[3 * i + j];
-                e.obs[j] = Q.obs[3 * i + j];
-            }
-            e.info = Q.inv_sigma2[i];
-            e.meta = i | (!(Q.obs[3 * i + 2] < 0) ? (int)0x80000000u : 0);
-        }
-    }
-    PoseProbDev* dp = (PoseProbDev*)d;
-    ORB_HIP_CHECK(hipMemcpyAsync(d, h, bProb + sizeof(PoseEdgeDev) * ne, hipMemcpyHostToDevice, stream_));
-    if (count > 0)
-    {
-        if (count <= pose_wide_max())
-            hipLaunchKernelGGL(k_pose_opt<kPoseThreadsWide>, dim3(count), dim3(kPoseThreadsWide), 0, stream_, dp, (const PoseEdgeDev*)(d + bProb),
-                               (double*)(d + bProb + bEdge), (uint8_t*)(d + bProb + bEdge + bErr));
-        else
-            hipLaunchKernelGGL(k_pose_opt<kPoseThreads>, dim3(count), dim3(kPoseThreads), 0, stream_, dp, (const PoseEdgeDev*)(d + bProb),
-                               (double*)(d + bProb + bEdge), (uint8_t*)(d + bProb + bEdge + bErr));
-    }
-    ORB_HIP_CHECK(hipGetLastError());
-    ORB_HIP_CHECK(hipMemcpyAsync(h, d, bProb, hipMemcpyDeviceToHost, stream_));
-    if (ne) ORB_HIP_CHECK(hipMemcpyAsync(hOut, d + bProb + bEdge + bErr, ne, hipMemcpyDeviceToHost, stream_));
-    ORB_HIP_CHECK(hipEventRecord(lastUse_, stream_));
-    lastUseSet_ = true;
-    ORB_HIP_CHECK(hipStreamSynchronize(stream_));
-    for (int f = 0; f < count; f++) {
-        const pose_problem& Q = P[f];
-        const PoseProbDev& pp = hp[f];
-        const uint8_t* o = hOut + pp.e0;
-        for (int i = 0, k = 0; i < Q.N; i++)
-            if (Q.has_mp[i]) {
-                outlier[f][i] = pp.nbad < 0 ? 0 : o[k];
-                k++;
-            }
-        if (pp.nbad < 0) {   // nInitialCorrespondences < 3: return 0, pose untouched
-            memcpy(Tcw_out + 16 * (size_t)f, Q.Tcw, sizeof(float) * 16);
-            ninliers[f] = 0;
-        } else {
-            host_se3_to_Tcw(pp.T, Tcw_out + 16 * (size_t)f);
-            ninliers[f] = pp.ne - pp.nbad;
-        }
-    }
-    return 0;
-}
+// ---------------------------------------------------------------- BaEngine (host)
+constexpr int kTiledMinPoses = kBaTiledMinPoses;   // 6 x 24 = 144 rows: the first n the LDS-resident dense solver cannot hold
 
 BaEngine::~BaEngine() {
     if (stream_) (void)hipStreamSynchronize(stream_);
@@ -3480,9 +1428,7 @@ int BaEngine::init() {
 }
 
 bool BaEngine::dense_solver(int n) const {
-    const size_t regShm = ldlt_reg_shm(n);
-    const size_t ldsBytes = sizeof(double) * ((size_t)n + (size_t)n * n);
-    return n <= kDenseMaxN && ((n < kLdltMax && regShm <= ldsMax_) || ldsBytes <= ldsMax_);
+    return n <= kDenseMaxN && dense_ldlt_plan(n, ldsMax_).kernel != DenseKernel::None;
 }
 
 // Carve every device buffer of the problem out of one grow-only arena.
@@ -4378,34 +2324,56 @@ static inline int nblk(int n, int b) { return (n + b - 1) / b; }
 // k_scale_chunks + k_csum; orbgpu_unit_set_scale_small_max lowers it so tests drive the chunked
 // path (and the device LM's scale == 0 branch) at oracle-sized problems
 static std::atomic<int> g_scale_small_max{2048 * 64};
-// The dense single-workgroup LDL^T of a pose system of n rows: the 1,024-thread panel kernel
-// (k_ldlt_reg) by default; ORBGPU_LDLT_DENSE=col / row picks the column-owner kernel (k_ldlt_col,
-// n <= 96) or the row-owner kernel (k_ldlt_row) for A/B runs.  Measured per local-BA call
-// (config 4, tools/ba_timing.py): panel 3.91-4.00 ms, column-owner 5.05 ms (136 us per solve
-// against 77), row-owner 8.63 ms (profiles/r04b_*, r04l_*).  All perform the oracle's operation
-// sequence.
-enum class DenseLdlt { Col, Reg, Row, Lds, T, D2 };
-static DenseLdlt dense_ldlt_kind(int n, bool use_reg) {
-    static const int pick = [] {
-        const char* e = std::getenv("ORBGPU_LDLT_DENSE");
-        if (!e) return 1;
-        if (!strcmp(e, "col")) return 0;
-        if (!strcmp(e, "row")) return 2;
-        if (!strcmp(e, "t")) return 3;
-        if (!strcmp(e, "2d")) return 4;
-        return 1;
-    }();
-    if (pick == 4 && n <= kLdltColMax) return DenseLdlt::D2;
-    if (pick == 2 && n <= kLdltRowMax) return DenseLdlt::Row;
-    if (pick == 3 && n <= kLdltColMax) return DenseLdlt::T;
-    if (pick == 0 && n <= kLdltColMax) return DenseLdlt::Col;
-    return use_reg ? DenseLdlt::Reg : DenseLdlt::Lds;
-}
 static bool scale_small(int nP, int nL) { return 6 * nP + 3 * nL <= g_scale_small_max.load(); }
 int debug_set_scale_small_max(int v) {
     if (v < 0 || v > 2048 * 64) return 1;
     g_scale_small_max.store(v);
     return 0;
+}
+
+// The stages of an LM trial that lm_solve, enqueue_lm_step and enqueue_lm_step_comm share.  gate:
+// the device LM's gate word (nullptr in the host-driven loop); lam / use_dev: the host's lambda or
+// the device's scal[5]; own: this rank adds the (replicated) pose terms.
+
+// Sharded, dense S: all-reduce the union-pattern tiles of S and b_s (packed)
+int BaEngine::allreduce_tiles(int n) {
+    hipStream_t s = stream_;
+    hipLaunchKernelGGL(k_tile_pack, dim3(nTiles_), dim3(256), 0, s, n, dS_, dTiles_, dPackBuf_);
+    double* pb = dPackBuf_ + (size_t)nTiles_ * 4096;
+    ORB_HIP_CHECK(hipMemcpyAsync(pb, dBs_, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+    ORB_HIP_CHECK(hipGetLastError());
+    if (int e = comm_->allreduce(dPackBuf_, (size_t)nTiles_ * 4096 + n, RedOp::Sum, s)) return e;
+    hipLaunchKernelGGL(k_tile_unpack, dim3(nTiles_), dim3(256), 0, s, n, dS_, dTiles_, dPackBuf_);
+    ORB_HIP_CHECK(hipMemcpyAsync(dBs_, pb, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
+// computeScale into scal[2]: one workgroup, or chunk trees + k_csum above scale_small's bound
+void BaEngine::launch_scale(double lam, int use_dev, int own, const int* gate) {
+    hipStream_t s = stream_;
+    const int nP = st_.nP, nL = st_.nL;
+    if (scale_small(nP, nL)) {
+        hipLaunchKernelGGL(k_scale, dim3(1), dim3(1024), 0, s, nP, nL, dX2_, dBp_, dBl_, lam, use_dev, dScal_,
+                           dScal_ + 2, own, gate);
+    } else {
+        const int nv = 6 * nP + 3 * nL;
+        hipLaunchKernelGGL(k_scale_chunks, dim3(nblk(nv, 256)), dim3(256), 0, s, nP, nL, dX2_, dBp_, dBl_, lam,
+                           use_dev, dScal_, tmpA0_, own, gate);
+        CsumList L0{tmpA0_, (nv + 63) / 64, tmpA1_, tmpA0_, dScal_ + 2};
+        hipLaunchKernelGGL(k_csum, dim3(1), dim3(1024), 0, s, L0, L0, gate);
+    }
+}
+
+// computeActiveErrors + activeRobustChi2 at the trial's poses and points, into scal[1]
+// (sys: the system linearisation's arguments)
+void BaEngine::launch_trial_errors(const LinArgs& sys, const int* gate) {
+    if (!st_.nE) return;
+    LinArgs la = sys;
+    la.linearize = 0;
+    la.out = dScal_ + 1;
+    la.run = gate;
+    hipLaunchKernelGGL(k_linearize, dim3(nblk(st_.nE, 256)), dim3(256), 0, stream_, la);
+    hipLaunchKernelGGL(k_chi2_finish, dim3(1), dim3(256), 0, stream_, la);
 }
 
 // OptimizationAlgorithmLevenberg::solve (optimization_algorithm_levenberg.cpp:59-164)
@@ -4451,15 +2419,10 @@ int BaEngine::lm_solve(int iteration, const volatile bool* stop, bool* terminate
     double rho = 0;
     int qmax = 0;
     const int n = 6 * nP;
-    const size_t ldsBytes = sizeof(double) * ((size_t)n + (size_t)n * n);
-    const int in_lds = ldsBytes <= ldsMax_ ? 1 : 0;
-    const size_t shm = in_lds ? ldsBytes : sizeof(double) * (size_t)n;
-    const size_t regShm = ldlt_reg_shm(n);
-    const bool use_reg = n < kLdltMax && regShm <= ldsMax_;   // b rides in column n
-    const DenseLdlt kind = dense_ldlt_kind(n, use_reg);
-    // n <= 128: register-resident single-workgroup LDL^T; S fits LDS: single-workgroup in LDS;
-    // larger: block-sparse tiled LDL^T in HBM (ldlt.hip, structure from build_structure)
-    if (!tiled_ && n > 0 && !use_reg && !in_lds) return -1;
+    // n < 128: register-resident single-workgroup LDL^T; S fits LDS: single-workgroup in LDS
+    // (dense_, ldlt_dense.hip); larger: block-sparse tiled LDL^T in HBM (ldlt.hip, structure
+    // from build_structure)
+    if (!tiled_ && n > 0 && dense_.kernel == DenseKernel::None) return -1;
     SysAddr sa{dS_, n, nullptr, nullptr, 0, nullptr};
     bool joined = false;
     do {
@@ -4488,54 +2451,25 @@ int BaEngine::lm_solve(int iteration, const volatile bool* stop, bool* terminate
             ORB_HIP_CHECK(hipGetLastError());
             const RedBuf rb[2] = {{sp_.tiles(), (size_t)sp_.nA() * 4096}, {dBs_, (size_t)n}};
             if (int e = comm_->allreduce(rb, 2, RedOp::Sum, s)) return e;
-        } else if (comm_ && nTiles_) {   // all-reduce the union-pattern tiles of S and b_s (packed)
-            hipLaunchKernelGGL(k_tile_pack, dim3(nTiles_), dim3(256), 0, s, n, dS_, dTiles_, dPackBuf_);
-            double* pb = dPackBuf_ + (size_t)nTiles_ * 4096;
-            ORB_HIP_CHECK(hipMemcpyAsync(pb, dBs_, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-            ORB_HIP_CHECK(hipGetLastError());
-            if (int e = comm_->allreduce(dPackBuf_, (size_t)nTiles_ * 4096 + n, RedOp::Sum, s)) return e;
-            hipLaunchKernelGGL(k_tile_unpack, dim3(nTiles_), dim3(256), 0, s, n, dS_, dTiles_, dPackBuf_);
-            ORB_HIP_CHECK(hipMemcpyAsync(dBs_, pb, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
+        } else if (comm_ && nTiles_) {
+            if (int e = allreduce_tiles(n)) return e;
         }
         if (tiled_ && distOk_) {
             if (int e = sp_.solve_dist(dBs_, dX2_, dScal_, s, comm_)) return e;
         } else if (tiled_) {
             if (int e = sp_.solve(dBs_, dX2_, dScal_, s)) return e;
-        } else if (kind == DenseLdlt::Col) {
-            hipLaunchKernelGGL(k_ldlt_col, dim3(1), dim3(256), 0, s, n, dS_, dBs_, dX2_, dScal_, nullptr);
-        } else if (kind == DenseLdlt::T) {
-            hipLaunchKernelGGL(k_ldlt_t, dim3(1), dim3(256), 0, s, n, dS_, dBs_, dX2_, dScal_, nullptr);
-        } else if (kind == DenseLdlt::D2) {
-            hipLaunchKernelGGL(k_ldlt_2d, dim3(1), dim3(256), 0, s, n, dS_, dBs_, dX2_, dScal_, nullptr);
-        } else if (kind == DenseLdlt::Row) {
-            hipLaunchKernelGGL(k_ldlt_row, dim3(1), dim3(128), 0, s, n, dS_, dBs_, dX2_, dScal_, nullptr);
-        } else if (kind == DenseLdlt::Reg) {
-            hipLaunchKernelGGL(k_ldlt_reg, dim3(1), dim3(kLdltThreads), regShm, s, n, dS_, dBs_, dX2_, dScal_, nullptr);
         } else {
-            hipLaunchKernelGGL(k_ldlt, dim3(1), dim3(256), shm + 16, s, n, dS_, dBs_, dX2_, dScal_, in_lds, nullptr);
+            dense_ldlt_launch(dense_, n, dS_, dBs_, dX2_, dScal_, nullptr, s);
         }
         // push + update
         if (nP + nL) hipLaunchKernelGGL(k_update, dim3(nblk(nP + nL, 256)), dim3(256), 0, s, S, dT_, dTbak_, dX_,
                                         dXbak_, dX2_, dHplA_, dHll_, dBl_, lambda_, use_dev, dScal_, nullptr);
         // computeActiveErrors + activeRobustChi2 ; computeScale
-        la.linearize = 0;
-        la.out = dScal_ + 1;
-        if (nE) {
-            hipLaunchKernelGGL(k_linearize, dim3(nblk(nE, 256)), dim3(256), 0, s, la);
-            hipLaunchKernelGGL(k_chi2_finish, dim3(1), dim3(256), 0, s, la);
-        } else if (comm_ && qmax > 0) {   // a rank without edges: its trial chi2 is 0 (the last trial's
+        launch_trial_errors(la, nullptr);
+        if (!nE && comm_ && qmax > 0) {   // a rank without edges: its trial chi2 is 0 (the last trial's
             ORB_HIP_CHECK(hipMemsetAsync(dScal_ + 1, 0, sizeof(double), s));   // all-reduced total otherwise)
         }
-        if (scale_small(nP, nL)) {
-            hipLaunchKernelGGL(k_scale, dim3(1), dim3(1024), 0, s, nP, nL, dX2_, dBp_, dBl_, lambda_, use_dev, dScal_,
-                               dScal_ + 2, own ? 1 : 0, nullptr);
-        } else {
-            const int nv = 6 * nP + 3 * nL;
-            hipLaunchKernelGGL(k_scale_chunks, dim3(nblk(nv, 256)), dim3(256), 0, s, nP, nL, dX2_, dBp_, dBl_, lambda_,
-                               use_dev, dScal_, tmpA0_, own ? 1 : 0, nullptr);
-            CsumList L0{tmpA0_, (nv + 63) / 64, tmpA1_, tmpA0_, dScal_ + 2};
-            hipLaunchKernelGGL(k_csum, dim3(1), dim3(1024), 0, s, L0, L0, nullptr);
-        }
+        launch_scale(lambda_, use_dev, own ? 1 : 0, nullptr);
         ORB_HIP_CHECK(hipGetLastError());
         if (comm_) {
             hScal_[32] = (stop && *stop) ? 1.0 : 0.0;
@@ -4595,6 +2529,7 @@ int BaEngine::lm_solve(int iteration, const volatile bool* stop, bool* terminate
 
 // SparseOptimizer::optimize (sparse_optimizer.cpp:354-418)
 int BaEngine::optimize(int iterations, const volatile bool* stop, int* its) {
+    dense_ = dense_ldlt_plan(6 * st_.nP, ldsMax_);   // (unused when tiled_)
     if (device_lm(iterations)) return optimize_device(iterations, stop, its);
     *its = 0;
     bool ok = true;
@@ -4678,30 +2613,19 @@ void BaEngine::enqueue_lm_step(bool first) {
     }
     if (first) hipLaunchKernelGGL(k_lambda_init, dim3(1), dim3(1024), 0, s, nP, nL, dHpp_, dHll_, dScal_, ctl + 2);
     const int n = 6 * nP;
-    const size_t ldsBytes = sizeof(double) * ((size_t)n + (size_t)n * n);
-    const int in_lds = ldsBytes <= ldsMax_ ? 1 : 0;
-    const size_t shm = in_lds ? ldsBytes : sizeof(double) * (size_t)n;
-    const size_t regShm = ldlt_reg_shm(n);
-    const bool use_reg = n < kLdltMax && regShm <= ldsMax_;   // b rides in column n
     const SysAddr sa{dS_, n, nullptr, nullptr, 0, nullptr};
     if (nE && !(fusedPrep && nP + nL))
         hipLaunchKernelGGL(k_point_prep, dim3(nblk(nE, 256)), dim3(256), 0, s, S, dHll_, dBl_, dHplA_, 0.0, 1, dScal_,
                            dEmat_, dCb_, ctl);
     if (S.nBlk) schur_launch(S.nBlk, blkChunks_, s, S, dEmat_, dHplA_, dCb_, dHpp_, dBp_, 0.0,
                                    1, dScal_, sa, dBs_, 1, (const uint8_t*)nullptr, ctl);
-    const DenseLdlt kind = dense_ldlt_kind(n, use_reg);
-    if (kind == DenseLdlt::Col) hipLaunchKernelGGL(k_ldlt_col, dim3(1), dim3(256), 0, s, n, dS_, dBs_, dX2_, dScal_, ctl);
-    else if (kind == DenseLdlt::T) hipLaunchKernelGGL(k_ldlt_t, dim3(1), dim3(256), 0, s, n, dS_, dBs_, dX2_, dScal_, ctl);
-    else if (kind == DenseLdlt::D2) hipLaunchKernelGGL(k_ldlt_2d, dim3(1), dim3(256), 0, s, n, dS_, dBs_, dX2_, dScal_, ctl);
-    else if (kind == DenseLdlt::Row) hipLaunchKernelGGL(k_ldlt_row, dim3(1), dim3(128), 0, s, n, dS_, dBs_, dX2_, dScal_, ctl);
-    else if (kind == DenseLdlt::Reg) hipLaunchKernelGGL(k_ldlt_reg, dim3(1), dim3(kLdltThreads), regShm, s, n, dS_, dBs_, dX2_, dScal_, ctl);
-    else hipLaunchKernelGGL(k_ldlt, dim3(1), dim3(256), shm + 16, s, n, dS_, dBs_, dX2_, dScal_, in_lds, ctl);
-    la.linearize = 0;
-    la.out = dScal_ + 1;
-    la.run = ctl;
+    dense_ldlt_launch(dense_, n, dS_, dBs_, dX2_, dScal_, ctl, s);
     if (fuse) {
         // the update inside the trial pass: edges at the trial's poses and points, the owners'
         // values to dTn_ / dXn_ (committed by k_lm_trial_end when the trial is accepted)
+        la.linearize = 0;
+        la.out = dScal_ + 1;
+        la.run = ctl;
         la.chunks = tmpB1_;
         la.fuse = 1;
         la.edgeBlocks = nblk(nE, 256);
@@ -4715,19 +2639,11 @@ void BaEngine::enqueue_lm_step(bool first) {
     } else {
         if (nP + nL) hipLaunchKernelGGL(k_update, dim3(nblk(nP + nL, 256)), dim3(256), 0, s, S, dT_, dTbak_, dX_, dXbak_,
                                         dX2_, dHplA_, dHll_, dBl_, 0.0, 1, dScal_, ctl);
-        if (nE) {
-            hipLaunchKernelGGL(k_linearize, dim3(nblk(nE, 256)), dim3(256), 0, s, la);
-            hipLaunchKernelGGL(k_chi2_finish, dim3(1), dim3(256), 0, s, la);
-        }
+        launch_trial_errors(la, ctl);
     }
+    // computeScale: k_lm_trial_end sums a small problem's terms itself; a large one's chunk path here
     const bool small = scale_small(nP, nL);
-    if (!small) {
-        const int nv = 6 * nP + 3 * nL;
-        hipLaunchKernelGGL(k_scale_chunks, dim3(nblk(nv, 256)), dim3(256), 0, s, nP, nL, dX2_, dBp_, dBl_, 0.0, 1,
-                           dScal_, tmpA0_, 1, ctl);
-        CsumList L0{tmpA0_, (nv + 63) / 64, tmpA1_, tmpA0_, dScal_ + 2};
-        hipLaunchKernelGGL(k_csum, dim3(1), dim3(1024), 0, s, L0, L0, ctl);
-    }
+    if (!small) launch_scale(0.0, 1, 1, ctl);
     hipLaunchKernelGGL(k_lm_trial_end, dim3(1), dim3(kTeThreads), 0, s, dLm_, dScal_, (volatile int*)hLm_, S, dT_, dTbak_,
                        dX_, dXbak_, dX2_, dBp_, dBl_, small ? 1 : 0,
                        fuse ? ChiFuse{tmpB0_, tmpB1_, nE} : ChiFuse{nullptr, nullptr, 0}, fuse ? dTn_ : nullptr,
@@ -4798,54 +2714,21 @@ int BaEngine::enqueue_lm_step_comm(bool first) {
     }
     // trial
     const int n = 6 * nP;
-    const size_t ldsBytes = sizeof(double) * ((size_t)n + (size_t)n * n);
-    const int in_lds = ldsBytes <= ldsMax_ ? 1 : 0;
-    const size_t shm = in_lds ? ldsBytes : sizeof(double) * (size_t)n;
-    const size_t regShm = ldlt_reg_shm(n);
-    const bool use_reg = n < kLdltMax && regShm <= ldsMax_;
-    const DenseLdlt kind = dense_ldlt_kind(n, use_reg);
     const SysAddr sa{dS_, n, nullptr, nullptr, 0, nullptr};
     if (nE) hipLaunchKernelGGL(k_point_prep, dim3(nblk(nE, 256)), dim3(256), 0, s, S, dHll_, dBl_, dHplA_, 0.0, 1, dScal_,
                                dEmat_, dCb_, ctl);
     if (n) ORB_HIP_CHECK(hipMemsetAsync(dS_, 0, sizeof(double) * (size_t)n * n, s));
     if (S.nBlk) schur_launch(S.nBlk, blkChunks_, s, S, dEmat_, dHplA_, dCb_, dHpp_, dBp_, 0.0, 1, dScal_, sa, dBs_,
                              own ? 1 : 0, (const uint8_t*)nullptr, ctl);
-    if (nTiles_) {   // the union-pattern tiles of S and b_s, packed
-        hipLaunchKernelGGL(k_tile_pack, dim3(nTiles_), dim3(256), 0, s, n, dS_, dTiles_, dPackBuf_);
-        double* pb = dPackBuf_ + (size_t)nTiles_ * 4096;
-        ORB_HIP_CHECK(hipMemcpyAsync(pb, dBs_, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-        ORB_HIP_CHECK(hipGetLastError());
-        if (int e = comm_->allreduce(dPackBuf_, (size_t)nTiles_ * 4096 + n, RedOp::Sum, s)) return e;
-        hipLaunchKernelGGL(k_tile_unpack, dim3(nTiles_), dim3(256), 0, s, n, dS_, dTiles_, dPackBuf_);
-        ORB_HIP_CHECK(hipMemcpyAsync(dBs_, pb, sizeof(double) * n, hipMemcpyDeviceToDevice, s));
-    }
-    if (kind == DenseLdlt::Col) hipLaunchKernelGGL(k_ldlt_col, dim3(1), dim3(256), 0, s, n, dS_, dBs_, dX2_, dScal_, ctl);
-    else if (kind == DenseLdlt::T) hipLaunchKernelGGL(k_ldlt_t, dim3(1), dim3(256), 0, s, n, dS_, dBs_, dX2_, dScal_, ctl);
-    else if (kind == DenseLdlt::D2) hipLaunchKernelGGL(k_ldlt_2d, dim3(1), dim3(256), 0, s, n, dS_, dBs_, dX2_, dScal_, ctl);
-    else if (kind == DenseLdlt::Row) hipLaunchKernelGGL(k_ldlt_row, dim3(1), dim3(128), 0, s, n, dS_, dBs_, dX2_, dScal_, ctl);
-    else if (kind == DenseLdlt::Reg) hipLaunchKernelGGL(k_ldlt_reg, dim3(1), dim3(kLdltThreads), regShm, s, n, dS_, dBs_, dX2_, dScal_, ctl);
-    else hipLaunchKernelGGL(k_ldlt, dim3(1), dim3(256), shm + 16, s, n, dS_, dBs_, dX2_, dScal_, in_lds, ctl);
+    if (nTiles_)
+        if (int e = allreduce_tiles(n)) return e;
+    dense_ldlt_launch(dense_, n, dS_, dBs_, dX2_, dScal_, ctl, s);
     if (nP + nL) hipLaunchKernelGGL(k_update, dim3(nblk(nP + nL, 256)), dim3(256), 0, s, S, dT_, dTbak_, dX_, dXbak_, dX2_,
                                     dHplA_, dHll_, dBl_, 0.0, 1, dScal_, ctl);
-    la.linearize = 0;
-    la.out = dScal_ + 1;
-    la.run = ctl;
-    if (nE) {
-        hipLaunchKernelGGL(k_linearize, dim3(nblk(nE, 256)), dim3(256), 0, s, la);
-        hipLaunchKernelGGL(k_chi2_finish, dim3(1), dim3(256), 0, s, la);
-    } else {   // (lm_solve's memset of chi2 for a rank without edges, here per trial)
+    launch_trial_errors(la, ctl);
+    if (!nE)   // (lm_solve's memset of chi2 for a rank without edges, here per trial)
         ORB_HIP_CHECK(hipMemsetAsync(dScal_ + 1, 0, sizeof(double), s));
-    }
-    if (scale_small(nP, nL)) {
-        hipLaunchKernelGGL(k_scale, dim3(1), dim3(1024), 0, s, nP, nL, dX2_, dBp_, dBl_, 0.0, 1, dScal_, dScal_ + 2,
-                           own ? 1 : 0, ctl);
-    } else {
-        const int nv = 6 * nP + 3 * nL;
-        hipLaunchKernelGGL(k_scale_chunks, dim3(nblk(nv, 256)), dim3(256), 0, s, nP, nL, dX2_, dBp_, dBl_, 0.0, 1,
-                           dScal_, tmpA0_, own ? 1 : 0, ctl);
-        CsumList L0{tmpA0_, (nv + 63) / 64, tmpA1_, tmpA0_, dScal_ + 2};
-        hipLaunchKernelGGL(k_csum, dim3(1), dim3(1024), 0, s, L0, L0, ctl);
-    }
+    launch_scale(0.0, 1, own ? 1 : 0, ctl);
     hipLaunchKernelGGL(k_lm_stop_in, dim3(1), dim3(64), 0, s, (const volatile int*)hLm_, dScal_ + 6);
     ORB_HIP_CHECK(hipGetLastError());
     {
@@ -5099,58 +2982,6 @@ int BaEngine::run(const ba_problem* P, const volatile bool* stop, ba_result* R, 
 
 // ---------------------------------------------------------------- unit entry points
 namespace orbgpu {
-int debug_ldlt(int n, const double* S, const double* b, double* x, int variant) {
-    if (variant == 2 || variant == 3) {   // block-sparse tiled solver (3: nested dissection); upper triangle read
-        std::vector<double> U((size_t)n * n, 0.0);
-        for (int i = 0; i < n; i++)
-            for (int j = i; j < n; j++) U[(size_t)i * n + j] = S[(size_t)i * n + j];
-        int ok = 0;
-        if (int e = ldlt_sparse_dense(n, U.data(), b, x, &ok, nullptr, variant == 3)) return e < 0 ? e : -1;
-        return ok;
-    }
-    if (variant == 0 && n >= kLdltMax) return -3;   // [S | b] needs a column register for b
-    double *dS = nullptr, *dB = nullptr, *dX = nullptr, *dScal = nullptr;
-    const size_t nn = (size_t)std::max(n, 1);
-    ORB_HIP_CHECK(hipMalloc(&dS, sizeof(double) * nn * nn));
-    ORB_HIP_CHECK(hipMalloc(&dB, sizeof(double) * nn));
-    ORB_HIP_CHECK(hipMalloc(&dX, sizeof(double) * nn));
-    ORB_HIP_CHECK(hipMalloc(&dScal, sizeof(double) * 16));
-    ORB_HIP_CHECK(hipMemcpy(dS, S, sizeof(double) * n * n, hipMemcpyHostToDevice));
-    ORB_HIP_CHECK(hipMemcpy(dB, b, sizeof(double) * n, hipMemcpyHostToDevice));
-    ORB_HIP_CHECK(hipMemset(dX, 0, sizeof(double) * nn));
-    if (variant == 5 || variant == 6 || variant == 7) {
-        if (n > kLdltColMax) return -3;
-        if (variant == 5) hipLaunchKernelGGL(k_ldlt_col, dim3(1), dim3(256), 0, 0, n, dS, dB, dX, dScal, nullptr);
-        else if (variant == 6) hipLaunchKernelGGL(k_ldlt_t, dim3(1), dim3(256), 0, 0, n, dS, dB, dX, dScal, nullptr);
-        else hipLaunchKernelGGL(k_ldlt_2d, dim3(1), dim3(256), 0, 0, n, dS, dB, dX, dScal, nullptr);
-    } else if (variant == 4) {
-        if (n > kLdltRowMax) return -3;
-        hipLaunchKernelGGL(k_ldlt_row, dim3(1), dim3(128), 0, 0, n, dS, dB, dX, dScal, nullptr);
-    } else if (variant == 0) {
-        const size_t shm = ldlt_reg_shm(n);
-        hipLaunchKernelGGL(k_ldlt_reg, dim3(1), dim3(kLdltThreads), shm, 0, n, dS, dB, dX, dScal, nullptr);
-    } else {
-        hipLaunchKernelGGL(k_ldlt, dim3(1), dim3(256), sizeof(double) * n + 16, 0, n, dS, dB, dX, dScal, 0, nullptr);
-    }
-    ORB_HIP_CHECK(hipGetLastError());
-    double sc[16];
-    ORB_HIP_CHECK(hipMemcpy(sc, dScal, sizeof(sc), hipMemcpyDeviceToHost));
-    ORB_HIP_CHECK(hipMemcpy(x, dX, sizeof(double) * n, hipMemcpyDeviceToHost));
-    (void)hipFree(dS); (void)hipFree(dB); (void)hipFree(dX); (void)hipFree(dScal);
-    return sc[3] != 0.0 ? 1 : 0;
-}
-
-// tiled factorisation only: A (n x n, upper = S) -> d on the diagonal, L in the strict lower
-// triangle, the eliminated rows above
-int debug_ldlt_factor(int n, const double* S, double* out) {
-    if (n <= 0) return 0;
-    std::vector<double> U((size_t)n * n, 0.0), b(n, 0.0), x(n, 0.0);
-    for (int i = 0; i < n; i++)
-        for (int j = i; j < n; j++) U[(size_t)i * n + j] = S[(size_t)i * n + j];
-    int ok = 0;
-    return ldlt_sparse_dense(n, U.data(), b.data(), x.data(), &ok, out, false);
-}
-
 __global__ void k_unit_wave_tree(const double* v, double* out) {
     const double t = wave_tree(v[threadIdx.x]);
     if (threadIdx.x == 0) *out = t;

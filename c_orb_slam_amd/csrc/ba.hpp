@@ -50,6 +50,8 @@ struct LmDev {
     double trialChi[kLmTrials], trialLam[kLmTrials], solveIni[kLmSolves], solveChi[kLmSolves];
 };
 
+struct LinArgs;   // k_linearize's arguments (ba.hip)
+
 class BaEngine {
 public:
     ~BaEngine();
@@ -85,6 +87,11 @@ private:
     void enqueue_lm_step(bool first);
     // the same step for a rank of a sharded run: lm_solve's kernels and exchanges, gated
     int enqueue_lm_step_comm(bool first);
+    // the trial stages the three drivers share (gate: the device LM's gate word or nullptr)
+    int allreduce_tiles(int n);
+    void launch_scale(double lam, int use_dev, int own, const int* gate);
+    void launch_trial_errors(const LinArgs& sys, const int* gate);
+    DensePlan dense_;   // the dense solver of this optimize() call's system (ldlt_dense.hip)
     // the structure builder of this call: the one-workgroup device builder (local-BA sizes,
     // unsharded), else the host lists below the device builder's edge threshold
     bool small_struct() const;

@@ -1,6 +1,7 @@
-// ba_math.hpp -- FP64 pieces shared by the optimisers (ba.hip, sim3opt.hip): Eigen
-// quaternion / g2o SE3Quat arithmetic as explicit IEEE operation sequences, the canonical
-// 64-wide reductions of oracle/ba.c (ora_csum), and the pivoted LDL^T of LinearSolverDense.
+// ba_math.hpp -- FP64 pieces shared by the optimisers (ba.hip, ldlt_dense.hip, pose_opt.hip,
+// sim3opt.hip): Eigen quaternion / g2o SE3Quat arithmetic as explicit IEEE operation sequences,
+// the canonical 64-wide reductions of oracle/ba.c (ora_csum), and the pivoted LDL^T of
+// LinearSolverDense.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -8,6 +9,7 @@
 #include <cmath>
 
 #include "ba.hpp"
+#include "detmath.hpp"
 
 namespace orbgpu {
 
@@ -142,6 +144,71 @@ HD void se3_mul(const Se3& a, const Se3& b, Se3& o) {
     se3_normalize(r);
     o = r;
 }
+
+// SE3Quat::exp (se3quat.h) of the update (omega, upsilon)
+__device__ __forceinline__ void se3_exp(const double* upd, Se3& out) {
+    const double* w = upd;
+    const double* u = upd + 3;
+    const double theta = sqrt((w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]);
+    const double Om[9] = {0, -w[2], w[1], w[2], 0, -w[0], -w[1], w[0], 0};
+    double Om2[9], R[9], V[9];
+    for (int i = 0; i < 3; i++)
+        for (int j = 0; j < 3; j++)
+            Om2[i * 3 + j] = (Om[i * 3] * Om[j] + Om[i * 3 + 1] * Om[3 + j]) + Om[i * 3 + 2] * Om[6 + j];
+    if (theta < 0.00001) {
+        for (int i = 0; i < 9; i++) {
+            R[i] = (((i % 4) == 0 ? 1.0 : 0.0) + Om[i]) + Om2[i];
+            V[i] = R[i];
+        }
+    } else {
+        double s, c;
+        detmath::sincos_d(theta, &s, &c);
+        const double a = s / theta, b = (1 - c) / (theta * theta);
+        const double cc = (theta - s) / ((theta * theta) * theta);
+        for (int i = 0; i < 9; i++) {
+            const double I = (i % 4) == 0 ? 1.0 : 0.0;
+            R[i] = (I + a * Om[i]) + b * Om2[i];
+            V[i] = (I + b * Om[i]) + cc * Om2[i];
+        }
+    }
+    quat_from_R(R, out.q);
+    for (int i = 0; i < 3; i++) out.t[i] = (V[i * 3] * u[0] + V[i * 3 + 1] * u[1]) + V[i * 3 + 2] * u[2];
+    out.pad = 0;
+    se3_normalize(out);
+}
+
+// Converter::toSE3Quat(Tcw) and back (row-major 4x4 float), on the host
+inline void host_se3_from_Tcw(const float* T, Se3& o) {
+    double R[9];
+    for (int r = 0; r < 3; r++)
+        for (int c = 0; c < 3; c++) R[r * 3 + c] = (double)T[r * 4 + c];
+    quat_from_R(R, o.q);
+    for (int r = 0; r < 3; r++) o.t[r] = (double)T[r * 4 + 3];
+    o.pad = 0;
+    se3_normalize(o);
+}
+
+inline void host_se3_to_Tcw(const Se3& s, float* T) {
+    double R[9];
+    quat_to_R(s.q, R);
+    for (int r = 0; r < 3; r++) {
+        for (int c = 0; c < 3; c++) T[r * 4 + c] = (float)R[r * 3 + c];
+        T[r * 4 + 3] = (float)s.t[r];
+    }
+    T[12] = T[13] = T[14] = 0.f;
+    T[15] = 1.f;
+}
+
+// the diagonal entries of a 6x6 upper triangle packed by rows (21 entries)
+constexpr int DIAG21[6] = {0, 6, 11, 15, 18, 20};
+
+// Device-resident LM (BaEngine::optimize_device): every kernel of a step takes a gate word that
+// k_lm_trial_end set for it; a step the decision made unnecessary runs as empty launches.
+// nullptr: always run (the host-driven path).
+#define BA_GATE(run)                  \
+    do {                              \
+        if ((run) && !*(run)) return; \
+    } while (0)
 
 // ---------------------------------------------------------------- canonical reductions
 // Canonical 64-tree across a wave: lane i (< off) += lane i + off for off = 32..1, result in

@@ -1,4 +1,5 @@
-// ldlt.hpp -- block-sparse (64x64-tile) LDL^T solve of the reduced pose system (see ldlt.hip).
+// ldlt.hpp -- block-sparse (64x64-tile) LDL^T solve of the reduced pose system (see ldlt.hip)
+// and the dense single-workgroup solvers of small systems (ldlt_dense.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -111,6 +112,21 @@ private:
     std::vector<int> hLevMaxT_;   // per level: the most tiles of one of its nodes (sweep launch shape)
     std::vector<int4> hSteps_;   // per panel step: first (panel, row job, pair job, panel job); + sentinel
 };
+
+// The dense single-workgroup solvers (ldlt_dense.hip) for systems below the block-sparse solver's
+// reach.  dense_ldlt_plan: which kernel takes n rows given the device's LDS per workgroup, and
+// its dynamic LDS bytes; dense_ldlt_launch: that kernel on [S | b] -> x, scal[3] = 1 on success
+// (0 on an exactly zero pivot), gated by ctl (the device LM's gate word) when it is not null.
+constexpr int kDenseMaxN = 144;   // >= every n the dense single-workgroup solvers take (n^2 doubles in LDS)
+enum class DenseKernel { None, Reg, Generic };   // k_ldlt_reg (register panels) / k_ldlt
+struct DensePlan {
+    DenseKernel kernel = DenseKernel::None;
+    size_t shm = 0;    // dynamic LDS bytes of the launch
+    int in_lds = 0;    // k_ldlt: S staged in LDS (else factored in place in HBM)
+};
+DensePlan dense_ldlt_plan(int n, size_t ldsMax);
+void dense_ldlt_launch(const DensePlan& plan, int n, double* S, const double* b, double* x, double* scal,
+                       const int* ctl, hipStream_t s);
 
 // Unit entry: dense host S (upper read) -> pattern of its nonzero 6 x 6 blocks -> sparse solve
 // (nd: nested-dissection order; else natural).  factor_out (optional, n x n, natural order

@@ -873,11 +873,11 @@ int orbgpu_unit_ldlt_solve(int n, const double* S, const double* b, double* x, i
 int orbgpu_unit_csum(const double* v, int n, double* out);
 /* tiled LDL^T factorisation only (n x n row-major, upper triangle read): out = d on the
  * diagonal, L in the strict lower triangle, eliminated rows in the strict upper. */
+int orbgpu_unit_ldlt_factor(int n, const double* S, double* out);
 /* PnPsolver batch work-area layout invariant (host only, no device): for n solvers with
  * N[k] correspondences, K[k] hypotheses and minSet[k], out4 = {device bytes allocated, device
  * end touched, host bytes allocated, host end touched}; ORB_OK iff everything touched fits. */
 int orbgpu_unit_pnp_layout(int n, const int* N, const int* K, const int* minSet, long long* out4);
-int orbgpu_unit_ldlt_factor(int n, const double* S, double* out);
 /* Host only (no device): the BA structure of one optimisation level (csrc/ba_struct.cpp,
  * initializeOptimization + buildIndexMapping + BlockSolver::buildStructure) packed into out:
  * [nE nP nL nBlk nPair | poseKf[nP] | landPt[nL] | ePose[nE] | eLand[nE] | lpStart[nL+1] |

@@ -1,7 +1,8 @@
 // ldlt_probe.hip -- phase timing (shader cycles) of k_ldlt_reg on an n x n SPD system (default 90).
-// build: compile this file, csrc/ldlt.hip (hipcc -c) and csrc/ordering.cpp (g++ -c), link with hipcc -> build/ldlt_probe
+// build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I c_orb_slam_amd/csrc tools/ldlt_probe.hip
+//        c_orb_slam_amd/csrc/{ldlt.hip,ordering.cpp,orb_match.hip} -o build/ldlt_probe
 #define ORB_LDLT_PROBE 1
-#include "../c_orb_slam_amd/csrc/ba.hip"
+#include "../c_orb_slam_amd/csrc/ldlt_dense.hip"
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -24,9 +25,9 @@ int main(int argc, char** argv) {
     hipMalloc(&dS, 8 * n * n); hipMalloc(&dB, 8 * n); hipMalloc(&dX, 8 * n); hipMalloc(&dScal, 128);
     hipMemcpy(dS, S.data(), 8 * n * n, hipMemcpyHostToDevice);
     hipMemcpy(dB, b.data(), 8 * n, hipMemcpyHostToDevice);
-    const size_t shm = orbgpu::ldlt_reg_shm(n);
+    const orbgpu::DensePlan plan{orbgpu::DenseKernel::Reg, orbgpu::ldlt_reg_shm(n), 0};   // k_ldlt_reg
     for (int rep = 0; rep < 3; rep++) {
-        hipLaunchKernelGGL(orbgpu::k_ldlt_reg, dim3(1), dim3(orbgpu::kLdltThreads), shm, 0, n, dS, dB, dX, dScal, nullptr);
+        orbgpu::dense_ldlt_launch(plan, n, dS, dB, dX, dScal, nullptr, nullptr);
         hipDeviceSynchronize();
     }
     long long p[256];

@@ -1,4 +1,4 @@
-// Phase timers of the column-owner dense LDL^T (k_ldlt_col in ba.hip) on one 90 x 90 system, plus
+// Phase timers of the column-owner dense LDL^T (k_ldlt_col in ldlt_dense.hip) on one 90 x 90 system, plus
 // the primitive costs it is built from: barrier of 4 waves, uniform-address LDS read chain, the
 // shared-denominator division.  s_memtime cycles (shader clock) and s_memrealtime (100 MHz) for
 // the clock rate.  hipcc --offload-arch=gfx950 -O3 -ffp-contract=off tools/micro/ldlt_col.hip

@@ -1,8 +1,8 @@
 // Cycle cost of k_pose_opt's serial trial pieces on one wave (gfx950): the 6x6 pivoted LDL^T solve
 // (pose_solve_w), se3_exp and se3_mul, each timed with clock64 over R dependent repetitions.
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -I c_orb_slam_amd/csrc
-//        tools/micro/pose_solve.hip c_orb_slam_amd/csrc/{ldlt.hip,ba_struct.cpp,ordering.cpp} -o build/pose_solve_micro
-#include "../../c_orb_slam_amd/csrc/ba.hip"
+//        tools/micro/pose_solve.hip c_orb_slam_amd/csrc/orb_match.hip -o build/pose_solve_micro
+#include "../../c_orb_slam_amd/csrc/pose_opt.hip"
 
 #include <cstring>
 #include <vector>
