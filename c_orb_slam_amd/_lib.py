@@ -205,6 +205,7 @@ def lib():
     L.Optimizer_PoseOptimization_batch_device.argtypes = [i32, vp, vp, vp, vp]
     L.Optimizer_OptimizeSim3.argtypes = [vp, vp, vp, P(i32)]
     L.Optimizer_OptimizeSim3_batch.argtypes = [i32, vp, vp, vp, vp]
+    L.Optimizer_OptimizeEssentialGraph.argtypes = [vp, i32, vp]
     L.Optimizer_PoseOptimization_frames_device.argtypes = [i32, vp, vp, vp, vp]
     L.Optimizer_pose_timing.argtypes = [i32, vp]
     L.orbgpu_unit_ba_struct.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, vp, C.c_longlong]
@@ -309,6 +310,17 @@ class sim3opt_problem(C.Structure):
                 ("obs1", C.c_void_p), ("obs2", C.c_void_p), ("inv_sigma2_1", C.c_void_p),
                 ("inv_sigma2_2", C.c_void_p), ("K1", C.c_float * 4), ("K2", C.c_float * 4), ("th2", C.c_float),
                 ("bFixScale", C.c_int)]
+
+
+class essgraph_problem(C.Structure):
+    _fields_ = [("nKF", C.c_int), ("Scw", C.c_void_p), ("ScwNonCorrected", C.c_void_p), ("fixed", C.c_void_p),
+                ("nE", C.c_int), ("edge_i", C.c_void_p), ("edge_j", C.c_void_p), ("edge_loop", C.c_void_p),
+                ("bFixScale", C.c_int), ("nMP", C.c_int), ("mp_pos", C.c_void_p), ("mp_ref", C.c_void_p)]
+
+
+class essgraph_result(C.Structure):
+    _fields_ = [("Scw", C.c_void_p), ("Tcw", C.c_void_p), ("mp_pos", C.c_void_p), ("chi2", C.c_void_p),
+                ("trace_cap", C.c_int), ("n_solves", C.c_int), ("lm_trials", C.c_int)]
 
 
 class ba_result(C.Structure):

@@ -42,6 +42,7 @@
 #include "detmath.hpp"
 #include "host_par.hpp"
 #include "ldlt.hpp"
+#include "lm_control.hpp"
 #include "orb_common.hpp"
 
 namespace orbgpu {
@@ -2488,27 +2489,12 @@ int BaEngine::lm_solve(int iteration, const volatile bool* stop, bool* terminate
             lambda_ = hScal_[5];
             use_dev = 0;
         }
-        const bool ok2 = hScal_[3] != 0.0;
-        double tempChi = hScal_[1];
-        if (!ok2) tempChi = DBL_MAX;
-        rho = currentChi - tempChi;
-        double scale = hScal_[2];
-        scale += 1e-3;
-        rho /= scale;
-        if (rho > 0 && std::isfinite(tempChi)) {
-            const double a3 = 2 * rho - 1;
-            double alpha = 1. - (a3 * a3) * a3;
-            alpha = std::fmin(alpha, 2. / 3.);
-            const double scaleFactor = std::fmax(1. / 3., alpha);
-            lambda_ *= scaleFactor;
-            ni_ = 2;
-            currentChi = tempChi;
-        } else {
-            lambda_ *= ni_;
-            ni_ *= 2;
-            if (nP + nL) hipLaunchKernelGGL(k_pop, dim3(nblk(nP + nL, 256)), dim3(256), 0, s, S, dT_, dTbak_, dX_,
-                                            dXbak_, nullptr);
-        }
+        bool accepted = false;
+        double tempChi = 0;
+        rho = lm_decide(hScal_[3] != 0.0, hScal_[1], hScal_[2], &lambda_, &ni_, &currentChi, &accepted, &tempChi);
+        if (!accepted && nP + nL)
+            hipLaunchKernelGGL(k_pop, dim3(nblk(nP + nL, 256)), dim3(256), 0, s, S, dT_, dTbak_, dX_, dXbak_,
+                               nullptr);
         qmax++;
         last_lm[1]++;
         trace_.trial_chi2.push_back(tempChi);
@@ -2516,14 +2502,7 @@ int BaEngine::lm_solve(int iteration, const volatile bool* stop, bool* terminate
     } while (rho < 0 && qmax < 10 && !stopped(stop));
     trace_.solve_ini_chi2.push_back(iniChi);
     trace_.solve_chi2.push_back(currentChi);
-    *terminate = false;
-    if (qmax == 10 || rho == 0) {
-        *terminate = true;
-        return 0;
-    }
-    if ((iniChi - currentChi) * 1e3 < iniChi) nBad_++;
-    else nBad_ = 0;
-    if (nBad_ >= 3) *terminate = true;
+    *terminate = lm_terminate(qmax, rho, iniChi, currentChi, &nBad_);
     return 0;
 }
 

@@ -22,101 +22,9 @@
 #include "ba_math.hpp"
 #include "detmath.hpp"
 #include "orb_common.hpp"
+#include "sim3_math.hpp"
 
 namespace orbgpu {
-
-struct Sim3d {   // g2o::Sim3: q = (x, y, z, w) like Eigen coeffs(), t, s
-    double q[4];
-    double t[3];
-    double s;
-};
-
-// g2o::Sim3(const Vector7d& update)  sim3.h:64-146
-__device__ __forceinline__ void sim3_exp(const double* upd, Sim3d& o) {
-    const double w0 = upd[0], w1 = upd[1], w2 = upd[2];
-    const double sigma = upd[6];
-    const double theta = sqrt((w0 * w0 + w1 * w1) + w2 * w2);
-    const double Om[9] = {0, -w2, w1, w2, 0, -w0, -w1, w0, 0};
-    double Om2[9], R[9];
-#pragma unroll
-    for (int i = 0; i < 3; i++)
-#pragma unroll
-        for (int j = 0; j < 3; j++)
-            Om2[i * 3 + j] = (Om[i * 3] * Om[j] + Om[i * 3 + 1] * Om[3 + j]) + Om[i * 3 + 2] * Om[6 + j];
-    const double s = detmath::exp_d(sigma);
-    const double eps = 0.00001;
-    double A, B, C, ra = 1.0, rb = 1.0;
-    const bool small = theta < eps;
-    if (!small) {
-        double sn, cs;
-        detmath::sincos_d(theta, &sn, &cs);
-        ra = sn / theta;
-        rb = (1 - cs) / (theta * theta);
-        if (fabs(sigma) < eps) {
-            C = 1;
-            const double theta2 = theta * theta;
-            A = (1 - cs) / theta2;
-            B = (theta - sn) / (theta2 * theta);
-        } else {
-            C = (s - 1) / sigma;
-            const double a = s * sn, b = s * cs;
-            const double theta2 = theta * theta, sigma2 = sigma * sigma;
-            const double c = theta2 + sigma2;
-            A = (a * sigma + (1 - b) * theta) / (theta * c);
-            B = (C - ((b - 1) * sigma + a * theta) / c) * 1. / theta2;
-        }
-    } else if (fabs(sigma) < eps) {
-        C = 1;
-        A = 1. / 2.;
-        B = 1. / 6.;
-    } else {
-        C = (s - 1) / sigma;
-        const double sigma2 = sigma * sigma;
-        A = ((sigma - 1) * s + 1) / sigma2;
-        B = ((0.5 * sigma2 - sigma + 1) * s) / (sigma2 * sigma);
-    }
-#pragma unroll
-    for (int i = 0; i < 9; i++) {
-        const double I = (i % 4) == 0 ? 1.0 : 0.0;
-        R[i] = small ? (I + Om[i]) + Om2[i] : (I + ra * Om[i]) + rb * Om2[i];
-    }
-    quat_from_R(R, o.q);
-    double W[9];
-#pragma unroll
-    for (int i = 0; i < 9; i++) W[i] = (A * Om[i] + B * Om2[i]) + C * ((i % 4) == 0 ? 1.0 : 0.0);
-#pragma unroll
-    for (int i = 0; i < 3; i++) o.t[i] = (W[i * 3] * upd[3] + W[i * 3 + 1] * upd[4]) + W[i * 3 + 2] * upd[5];
-    o.s = s;
-}
-
-// operator*  sim3.h:264-270
-__device__ __forceinline__ void sim3_mul(const Sim3d& a, const Sim3d& b, Sim3d& o) {
-    Sim3d r;
-    r.q[3] = ((a.q[3] * b.q[3] - a.q[0] * b.q[0]) - a.q[1] * b.q[1]) - a.q[2] * b.q[2];
-    r.q[0] = ((a.q[3] * b.q[0] + a.q[0] * b.q[3]) + a.q[1] * b.q[2]) - a.q[2] * b.q[1];
-    r.q[1] = ((a.q[3] * b.q[1] + a.q[1] * b.q[3]) + a.q[2] * b.q[0]) - a.q[0] * b.q[2];
-    r.q[2] = ((a.q[3] * b.q[2] + a.q[2] * b.q[3]) + a.q[0] * b.q[1]) - a.q[1] * b.q[0];
-    double rt[3];
-    quat_rotate(a.q, b.t, rt);
-#pragma unroll
-    for (int i = 0; i < 3; i++) r.t[i] = a.s * rt[i] + a.t[i];
-    r.s = a.s * b.s;
-    o = r;
-}
-
-// inverse  sim3.h:235-238
-__device__ __forceinline__ void sim3_inverse(const Sim3d& T, Sim3d& o) {
-    Sim3d r;
-    r.q[0] = -T.q[0];
-    r.q[1] = -T.q[1];
-    r.q[2] = -T.q[2];
-    r.q[3] = T.q[3];
-    const double ms = -1. / T.s;
-    const double v[3] = {ms * T.t[0], ms * T.t[1], ms * T.t[2]};
-    quat_rotate(r.q, v, r.t);
-    r.s = 1. / T.s;
-    o = r;
-}
 
 // edge in HBM: 32 B
 struct S3EdgeDev {

@@ -18,7 +18,8 @@ import threading
 
 import numpy as np
 
-from ._lib import ba_problem, ba_result, check, lib, pose_problem, ptr, sim3opt_problem
+from ._lib import (ba_problem, ba_result, check, essgraph_problem, essgraph_result, lib, pose_problem, ptr,
+                   sim3opt_problem)
 
 _FIELDS = (("kf_id", np.int32), ("kf_Tcw", np.float32), ("kf_local", np.uint8), ("kf_cam", np.float32),
            ("pt_id", np.int32), ("pt_pos", np.float32), ("edge_pt", np.int32), ("edge_kf", np.int32),
@@ -143,6 +144,38 @@ def OptimizeSim3Batch(problems, S12s):
     n = np.zeros(max(F, 1), np.int32)
     check(lib().Optimizer_OptimizeSim3_batch(F, probs, ptr(S), eptr, ptr(n)), "Optimizer_OptimizeSim3")
     return n[:F], S[:F], [e[:len(k["valid"])].astype(bool) for e, k in zip(er, keep)]
+
+
+# ------------------------------------------------------------------ OptimizeEssentialGraph
+def OptimizeEssentialGraph(problem, nIterations=20):
+    """Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3, CorrectedSim3,
+    LoopConnections, bFixScale) (Optimizer.cc:781-1044; LoopClosing.cc:567).
+
+    problem: dict with Scw (nKF x 8: q xyzw, t, s; vScw), ScwNonCorrected (nKF x 8, optional: Scw),
+    fixed (nKF), edge_i / edge_j / edge_loop (nE), bFixScale, and optionally mp_pos (nMP x 3), mp_ref (nMP).
+    -> dict(Scw: CorrectedSiw, Tcw: the SetPose arguments (nKF x 4 x 4), mp_pos, chi2: before the first solve
+    and after each, n_solves, lm_trials)."""
+    Scw = np.ascontiguousarray(problem["Scw"], np.float64)
+    nKF = len(Scw)
+    Snc = np.ascontiguousarray(problem.get("ScwNonCorrected", Scw), np.float64)
+    fixed = np.ascontiguousarray(problem["fixed"], np.uint8)
+    ei = np.ascontiguousarray(problem["edge_i"], np.int32)
+    ej = np.ascontiguousarray(problem["edge_j"], np.int32)
+    el = np.ascontiguousarray(problem["edge_loop"], np.uint8)
+    mp = np.ascontiguousarray(problem.get("mp_pos", np.zeros((0, 3))), np.float32)
+    ref = np.ascontiguousarray(problem.get("mp_ref", np.zeros(0)), np.int32)
+    nE, nMP = len(ei), len(ref)
+    if (Scw.shape != (nKF, 8) or Snc.shape != (nKF, 8) or fixed.shape != (nKF,) or ej.shape != (nE,)
+            or el.shape != (nE,) or mp.shape != (nMP, 3)):
+        raise ValueError("OptimizeEssentialGraph: inconsistent arrays")
+    P = essgraph_problem(nKF, ptr(Scw), ptr(Snc), ptr(fixed), nE, ptr(ei), ptr(ej), ptr(el),
+                         int(bool(problem["bFixScale"])), nMP, ptr(mp), ptr(ref))
+    cap = int(nIterations) + 1 if nIterations >= 0 else 1
+    oS, oT, oX, chi = np.zeros((nKF, 8)), np.zeros((nKF, 4, 4), np.float32), np.zeros((nMP, 3), np.float32), np.zeros(cap)
+    R = essgraph_result(ptr(oS), ptr(oT), ptr(oX), ptr(chi), cap, 0, 0)
+    check(lib().Optimizer_OptimizeEssentialGraph(C.byref(P), int(nIterations), C.byref(R)),
+          "Optimizer_OptimizeEssentialGraph")
+    return dict(Scw=oS, Tcw=oT, mp_pos=oX, chi2=chi[:R.n_solves + 1], n_solves=R.n_solves, lm_trials=R.lm_trials)
 
 
 # ------------------------------------------------------------------ PoseOptimization

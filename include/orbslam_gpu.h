@@ -731,6 +731,48 @@ int Optimizer_OptimizeSim3_batch(int count, const sim3opt_problem* P, double* S1
                                  int* nIn);
 
 /* ======================================================================
+ * Essential-graph optimisation  (reference Optimizer::OptimizeEssentialGraph,
+ * src/Optimizer.cc:781-1044; include/Optimizer.h:52-56; called from
+ * LoopClosing::CorrectLoop, LoopClosing.cc:567)
+ * One VertexSim3Expmap per keyframe, EdgeSim3 with information I7 and no
+ * robust kernel (numeric Jacobians), BlockSolver_7_3 without marginalised
+ * vertices, Levenberg with setUserLambdaInit(1e-16), optimize(20).
+ * Which edges exist (spanning tree, loop edges, covisibility >= minFeat,
+ * LoopConnections, de-duplication) is decided by the caller; the same
+ * vertex pair may appear in several edges, which are summed.
+ * ====================================================================== */
+typedef struct essgraph_problem {
+    int nKF;                  /* non-bad keyframes, caller's order (>= 1) */
+    const double* Scw;        /* nKF x 8 (q xyzw, t, s): vScw, the initial estimates; q of unit length */
+    const double* ScwNonCorrected; /* nKF x 8: NonCorrectedSim3[kf] where present, else the Scw row */
+    const uint8_t* fixed;     /* nKF: 1 = pLoopKF */
+    int nE;
+    const int32_t* edge_i;    /* vertex(0) */
+    const int32_t* edge_j;    /* vertex(1) */
+    const uint8_t* edge_loop; /* 1: LoopConnections edge (both sides from Scw), 0: normal edge */
+    int bFixScale;
+    int nMP;                  /* map points to correct (0 allowed) */
+    const float* mp_pos;      /* nMP x 3 */
+    const int32_t* mp_ref;    /* nMP: vertex index of nIDr, -1 = leave the point */
+} essgraph_problem;
+typedef struct essgraph_result {
+    double* Scw;       /* nKF x 8: CorrectedSiw */
+    float* Tcw;        /* nKF x 16: the SetPose argument [R | t/s] */
+    float* mp_pos;     /* nMP x 3 */
+    double* chi2;      /* trace_cap: chi2 before the first solve, then after each */
+    int trace_cap, n_solves, lm_trials;
+} essgraph_result;
+
+/* static void Optimizer::OptimizeEssentialGraph(pMap, pLoopKF, pCurKF, NonCorrectedSim3,
+ * CorrectedSim3, LoopConnections, bFixScale).  Measurement of edge (i, j): Sjw * Swi, from Scw
+ * on a LoopConnections edge, else from ScwNonCorrected.  nIterations: the reference passes 20;
+ * 0 evaluates the initial chi2 and does the write-back from the inputs.  A free vertex without
+ * an edge is returned unchanged.  n_solves = LM iterations run, lm_trials = factorisations.
+ * ORB_E_INVALID (before any device work): null pointers, indices out of range, edge_i ==
+ * edge_j, non-finite entries, s <= 0, nIterations < 0.  ORB_E_CAPACITY beyond 458752 edges. */
+int Optimizer_OptimizeEssentialGraph(const essgraph_problem* P, int nIterations, essgraph_result* R);
+
+/* ======================================================================
  * Motion-only pose optimisation  (reference Optimizer::PoseOptimization,
  * src/Optimizer.cc:239-451; include/Optimizer.h:48)
  * One SE3 vertex, one unary edge per keypoint with a map point
