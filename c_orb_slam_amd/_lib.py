@@ -241,6 +241,9 @@ def lib():
     L.orbgpu_unit_set_posegraph_check.argtypes = [i32]
     L.orbgpu_unit_ba_struct_all.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp, vp, i32, i32, vp, C.c_longlong, vp]
     L.orbgpu_unit_nd_order.argtypes = [i32, vp, vp, i32, vp, vp, vp]
+    L.orbgpu_unit_sim3.argtypes = [i32, i32, vp, vp, vp, vp]
+    L.orbgpu_unit_essgraph_stage.argtypes = [vp, C.c_double, vp]
+    L.orbgpu_unit_set_ess_dense_max.argtypes = [i32]
     L.orbgpu_debug_prof.argtypes = [vp]
     L.orbgpu_debug_prof_match.argtypes = [vp]
     L.orbgpu_debug_prof_extract.argtypes = [vp]
@@ -321,6 +324,13 @@ class essgraph_problem(C.Structure):
 class essgraph_result(C.Structure):
     _fields_ = [("Scw", C.c_void_p), ("Tcw", C.c_void_p), ("mp_pos", C.c_void_p), ("chi2", C.c_void_p),
                 ("trace_cap", C.c_int), ("n_solves", C.c_int), ("lm_trials", C.c_int)]
+
+
+class essgraph_stage(C.Structure):
+    _fields_ = [("solver", C.c_int), ("nV", C.c_int), ("ok", C.c_int), ("sysIdx", C.c_void_p), ("meas", C.c_void_p),
+                ("err", C.c_void_p), ("chi2e", C.c_void_p), ("J", C.c_void_p), ("H", C.c_void_p), ("b", C.c_void_p),
+                ("x_solve", C.c_void_p), ("x", C.c_void_p), ("est_trial", C.c_void_p), ("chi2e_trial", C.c_void_p),
+                ("chi2", C.c_double), ("chi2_trial", C.c_double), ("scale", C.c_double)]
 
 
 class ba_result(C.Structure):

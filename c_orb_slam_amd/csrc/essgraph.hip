@@ -18,9 +18,13 @@
 //   - the host takes the accept / reject decision from the four scalars (lm_control.hpp, the one
 //     BaEngine::lm_solve uses).
 // Finish kernels: CorrectedSiw^-1, Tcw = [R | t/s] as float, and the map-point correction.
+// Test-only entries (orbgpu_unit_essgraph_stage, orbgpu_unit_sim3): one linearisation and one
+// trial through the same launches with every intermediate buffer copied out, and the Sim3
+// functions one item per thread.
 #include "essgraph.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <cstring>
 #include <vector>
 
@@ -258,6 +262,58 @@ __global__ void __launch_bounds__(256) k_ess_points(int nMP, const int32_t* ref,
     for (int i = 0; i < 3; i++) pos[3 * (size_t)p + i] = (float)w[i];
 }
 
+// ---------------------------------------------------------------- unit entries' kernels
+// orbgpu_unit_sim3: one item per thread through the inline functions above
+__global__ void __launch_bounds__(256) k_unit_sim3(int op, int n, const double* a, const double* b, const double* c,
+                                                   double* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const Sim3d* A = (const Sim3d*)a;
+    const Sim3d* B = (const Sim3d*)b;
+    if (op == 0) {
+        Sim3d o;
+        sim3_exp(a + 7 * (size_t)i, o);
+        ((Sim3d*)out)[i] = o;
+    } else if (op == 1) {
+        sim3_log(A[i], out + 7 * (size_t)i);
+    } else if (op == 2) {
+        Sim3d o;
+        sim3_mul(A[i], B[i], o);
+        ((Sim3d*)out)[i] = o;
+    } else if (op == 3) {
+        Sim3d o;
+        sim3_inverse(A[i], o);
+        ((Sim3d*)out)[i] = o;
+    } else if (op == 4) {
+        sim3_map(A[i], b + 3 * (size_t)i, out + 3 * (size_t)i);
+    } else {
+        ess_error(A[i], B[i], ((const Sim3d*)c)[i], out + 7 * (size_t)i);
+    }
+}
+
+// orbgpu_unit_essgraph_stage: the upper triangle of H in system order out of the solver's storage
+// (an element whose tile the block-sparse pattern does not hold is zero)
+__global__ void __launch_bounds__(256) k_ess_dump_h(int n, EssAddr sa, double* out) {
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)n * n) return;
+    const int r = (int)(idx / n), c = (int)(idx % n);
+    double v = 0;
+    if (r <= c) {
+        bool held = true;
+        if (!sa.dense) {
+            int a = sa.prow[r / 7] + r % 7, b = sa.prow[c / 7] + c % 7;
+            if (a > b) {
+                const int t = a;
+                a = b;
+                b = t;
+            }
+            held = sa.slot_of[(size_t)(a >> 6) * sa.nt + (b >> 6)] >= 0;
+        }
+        if (held) v = *sa.at(r, c);
+    }
+    out[idx] = v;
+}
+
 // ---------------------------------------------------------------- host
 class EssGraphEngine {
 public:
@@ -278,7 +334,11 @@ public:
         ldsMax_ = prop.sharedMemPerBlock > 2048 ? prop.sharedMemPerBlock - 1024 : 0;
         return 0;
     }
-    int run(const essgraph_problem* P, int nIterations, essgraph_result* R);
+    // stage == nullptr: the optimisation (R written).  Else the unit entry: one full pass and one
+    // trial at stageLambda through the launches the LM loop uses, the intermediate buffers copied
+    // into *stage; R and nIterations are not used.
+    int run(const essgraph_problem* P, int nIterations, essgraph_result* R, essgraph_stage* stage = nullptr,
+            double stageLambda = 0);
 
 private:
     hipStream_t stream_ = nullptr;
@@ -291,9 +351,19 @@ private:
 
 static inline int ess_nblk(int n, int b) { return (n + b - 1) / b; }
 
-int EssGraphEngine::run(const essgraph_problem* P, int nIterations, essgraph_result* R) {
+// rows the dense solver takes (orbgpu_unit_set_ess_dense_max lowers it so tests put a small
+// system through the block-sparse solver)
+static std::atomic<int> g_ess_dense_max{kDenseMaxN};
+int debug_set_ess_dense_max(int rows) {
+    if (rows < 0 || rows > kDenseMaxN) return 1;
+    g_ess_dense_max.store(rows);
+    return 0;
+}
+
+int EssGraphEngine::run(const essgraph_problem* P, int nIterations, essgraph_result* R, essgraph_stage* stage,
+                        double stageLambda) {
     hipStream_t s = stream_;
-    const int nKF = P->nKF, nE = P->nE, nMP = P->nMP;
+    const int nKF = P->nKF, nE = P->nE, nMP = stage ? 0 : P->nMP;   // the stage entry moves no map points
     const int fix = P->bFixScale ? 1 : 0;
     if (ess_nblk(nE, 64) > kEssSumMaxChunks) return -3;
     // ---- system vertices: free with at least one edge, in the caller's order
@@ -334,11 +404,11 @@ int EssGraphEngine::run(const essgraph_problem* P, int nIterations, essgraph_res
     const int nBlk = (int)blkA.size();
     blkStart.push_back((int)ents.size());
     // ---- solver of this call
-    const bool optimise = nIterations > 0 && nE > 0 && nV > 0;
+    const bool optimise = (stage || nIterations > 0) && nE > 0 && nV > 0;
     DensePlan dense;
     bool tiled = false;
     if (optimise) {
-        if (n <= kDenseMaxN) dense = dense_ldlt_plan(n, ldsMax_);
+        if (n <= g_ess_dense_max.load()) dense = dense_ldlt_plan(n, ldsMax_);
         if (dense.kernel == DenseKernel::None) {
             std::vector<int> adjStart(nV + 1, 0), adj;
             std::vector<std::vector<int>> nb(nV);
@@ -377,6 +447,7 @@ int EssGraphEngine::run(const essgraph_problem* P, int nIterations, essgraph_res
     const size_t oChi = carve(sizeof(double) * nE), oJ = carve(sizeof(double) * kEssJ * nE);
     const size_t oB = carve(sizeof(double) * n), oX = carve(sizeof(double) * n), oScal = carve(sizeof(double) * 16);
     const size_t oS = carve(optimise && !tiled ? sizeof(double) * (size_t)n * n : 8), oTcw = carve(sizeof(float) * 16 * nKF);
+    const size_t oH = carve(stage && stage->H && optimise ? sizeof(double) * (size_t)n * n : 8);   // the stage entry's copy of H
     if (off > cap_) {
         if (arena_) (void)hipFree(arena_);
         arena_ = nullptr;
@@ -433,12 +504,16 @@ int EssGraphEngine::run(const essgraph_problem* P, int nIterations, essgraph_res
         ORB_HIP_CHECK(hipStreamSynchronize(s));
         return 0;
     };
-    R->n_solves = 0;
-    R->lm_trials = 0;
+    if (R) R->n_solves = R->lm_trials = 0;
     int nTrace = 0;
     const auto trace = [&](double c) {
-        if (nTrace < R->trace_cap) R->chi2[nTrace] = c;
+        if (R && nTrace < R->trace_cap) R->chi2[nTrace] = c;
         nTrace++;
+    };
+    // the stage entry's device-to-host copies (a NULL destination is skipped)
+    const auto fetch = [&](void* dst, const void* src, size_t bytes) -> int {
+        if (dst && bytes) ORB_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s));
+        return 0;
     };
     // ---- measurements and the initial chi2
     if (nE) {
@@ -452,33 +527,67 @@ int EssGraphEngine::run(const essgraph_problem* P, int nIterations, essgraph_res
     if (optimise) {
         const EssAddr sa = tiled ? EssAddr{nullptr, n, sp_.addr().slot_of, sp_.addr().tiles, sp_.addr().nt, sp_.addr().prow}
                                  : EssAddr{dS, n, nullptr, nullptr, 0, nullptr};
+        // one LM trial in three steps, shared by the loop below and the stage entry
+        const auto assemble = [&](double lambda) -> int {
+            if (tiled) {
+                if (int e = sp_.zero(s)) return e;
+            } else {
+                ORB_HIP_CHECK(hipMemsetAsync(dS, 0, sizeof(double) * (size_t)n * n, s));
+            }
+            hipLaunchKernelGGL(k_ess_assemble, dim3(nBlk), dim3(64), 0, s, (const int*)(d + oBlkS),
+                               (const int*)(d + oBlkA), (const int*)(d + oBlkB), (const int*)(d + oEnt),
+                               (const double*)E.J, (const double*)E.err, lambda, sa, dB);
+            return 0;
+        };
+        const auto solve = [&]() -> int {
+            if (tiled) return sp_.solve(dB, dX, dScal, s);
+            dense_ldlt_launch(dense, n, dS, dB, dX, dScal, nullptr, s);
+            return 0;
+        };
+        const auto update_and_evaluate = [&](double lambda) -> int {
+            hipLaunchKernelGGL(k_ess_update, dim3(ess_nblk(nKF, 256)), dim3(256), 0, s, nKF, fix, dSys, dEst, dBak, dX);
+            lin(0, dScal + 1);
+            hipLaunchKernelGGL(k_ess_sum, dim3(1), dim3(kEssSumThreads), shmN, s, 1, n, (const double*)dX, (const double*)dB, lambda,
+                               dScal + 2);
+            return read_scal();
+        };
+        if (stage) {
+            lin(1, dScal + 0);
+            if (fetch(stage->err, E.err, sizeof(double) * 7 * nE) || fetch(stage->chi2e, dChi, sizeof(double) * nE) ||
+                fetch(stage->J, E.J, sizeof(double) * kEssJ * nE))
+                return -2;
+            if (int e = assemble(stageLambda)) return e;
+            if (stage->H) {
+                double* dH = (double*)(d + oH);
+                hipLaunchKernelGGL(k_ess_dump_h, dim3((unsigned)(((size_t)n * n + 255) / 256)), dim3(256), 0, s, n, sa, dH);
+                if (fetch(stage->H, dH, sizeof(double) * (size_t)n * n)) return -2;
+            }
+            if (fetch(stage->b, dB, sizeof(double) * n)) return -2;
+            if (int e = solve()) return e;
+            if (fetch(stage->x_solve, dX, sizeof(double) * n)) return -2;
+            if (int e = update_and_evaluate(stageLambda)) return e;
+            if (fetch(stage->x, dX, sizeof(double) * n) || fetch(stage->est_trial, dEst, sizeof(Sim3d) * nKF) ||
+                fetch(stage->chi2e_trial, dChi, sizeof(double) * nE))
+                return -2;
+            ORB_HIP_CHECK(hipStreamSynchronize(s));
+            stage->solver = tiled ? 1 : 0;
+            stage->ok = hScal_[3] != 0.0;
+            stage->chi2 = hScal_[0];
+            stage->chi2_trial = hScal_[1];
+            stage->scale = hScal_[2];
+        }
         double lambda = 1e-16, ni = 2;
         int nBad = 0;
-        bool term = false;
+        bool term = stage != nullptr;
         for (int it = 0; it < nIterations && !term; it++) {
             lin(1, dScal + 0);
             double currentChi = 0, iniChi = 0, rho = 0;
             bool haveChi = false;
             int qmax = 0;
             do {
-                if (tiled) {
-                    if (int e = sp_.zero(s)) return e;
-                } else {
-                    ORB_HIP_CHECK(hipMemsetAsync(dS, 0, sizeof(double) * (size_t)n * n, s));
-                }
-                hipLaunchKernelGGL(k_ess_assemble, dim3(nBlk), dim3(64), 0, s, (const int*)(d + oBlkS),
-                                   (const int*)(d + oBlkA), (const int*)(d + oBlkB), (const int*)(d + oEnt),
-                                   (const double*)E.J, (const double*)E.err, lambda, sa, dB);
-                if (tiled) {
-                    if (int e = sp_.solve(dB, dX, dScal, s)) return e;
-                } else {
-                    dense_ldlt_launch(dense, n, dS, dB, dX, dScal, nullptr, s);
-                }
-                hipLaunchKernelGGL(k_ess_update, dim3(ess_nblk(nKF, 256)), dim3(256), 0, s, nKF, fix, dSys, dEst, dBak, dX);
-                lin(0, dScal + 1);
-                hipLaunchKernelGGL(k_ess_sum, dim3(1), dim3(kEssSumThreads), shmN, s, 1, n, (const double*)dX, (const double*)dB, lambda,
-                                   dScal + 2);
-                if (int e = read_scal()) return e;
+                if (int e = assemble(lambda)) return e;
+                if (int e = solve()) return e;
+                if (int e = update_and_evaluate(lambda)) return e;
                 if (!haveChi) {
                     currentChi = iniChi = hScal_[0];
                     haveChi = true;
@@ -496,6 +605,26 @@ int EssGraphEngine::run(const essgraph_problem* P, int nIterations, essgraph_res
             term = lm_terminate(qmax, rho, iniChi, currentChi, &nBad);
         }
     }
+    if (stage) {
+        if (!optimise) {   // nothing to solve: the full pass alone
+            if (nE) {
+                lin(1, dScal + 0);
+                if (fetch(stage->err, E.err, sizeof(double) * 7 * nE) || fetch(stage->chi2e, dChi, sizeof(double) * nE) ||
+                    fetch(stage->J, E.J, sizeof(double) * kEssJ * nE))
+                    return -2;
+            }
+            stage->solver = -1;
+            stage->ok = 0;
+            stage->chi2 = hScal_[0];
+            stage->chi2_trial = stage->scale = 0;
+        }
+        stage->nV = nV;
+        if (stage->sysIdx) std::copy(sysIdx.begin(), sysIdx.end(), stage->sysIdx);
+        if (fetch(stage->meas, E.meas, sizeof(Sim3d) * nE)) return -2;
+        ORB_HIP_CHECK(hipGetLastError());
+        ORB_HIP_CHECK(hipStreamSynchronize(s));
+        return 0;
+    }
     // ---- write-back
     hipLaunchKernelGGL(k_ess_finish, dim3(ess_nblk(nKF, 256)), dim3(256), 0, s, nKF, (const Sim3d*)dEst,
                        (Sim3d*)(d + oSwc), (float*)(d + oTcw));
@@ -510,15 +639,56 @@ int EssGraphEngine::run(const essgraph_problem* P, int nIterations, essgraph_res
     return 0;
 }
 
-int essgraph_run(const essgraph_problem* P, int nIterations, essgraph_result* R) {
+static EssGraphEngine* ess_engine(int* rc) {
     thread_local EssGraphEngine* e = nullptr;
     thread_local int erc = 0;
     if (!e) {
         e = new EssGraphEngine();
         erc = e->init();
     }
+    *rc = erc;
+    return e;
+}
+
+int essgraph_run(const essgraph_problem* P, int nIterations, essgraph_result* R) {
+    int erc = 0;
+    EssGraphEngine* e = ess_engine(&erc);
     if (erc) return erc;
     return e->run(P, nIterations, R);
+}
+
+int essgraph_stage_run(const essgraph_problem* P, double lambda, essgraph_stage* out) {
+    int erc = 0;
+    EssGraphEngine* e = ess_engine(&erc);
+    if (erc) return erc;
+    return e->run(P, 0, nullptr, out, lambda);
+}
+
+int essgraph_unit_sim3(int op, int n, const double* a, const double* b, const double* c, double* out) {
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return -4;
+    if (n == 0) return 0;
+    const size_t inA = op == 0 ? 7 : 8, inB = op == 2 || op == 5 ? 8 : op == 4 ? 3 : 0, inC = op == 5 ? 8 : 0;
+    const size_t nOut = op == 1 || op == 5 ? 7 : op == 4 ? 3 : 8;
+    const size_t per = inA + inB + inC + nOut;
+    double* dm = nullptr;
+    ORB_HIP_CHECK(hipMalloc((void**)&dm, sizeof(double) * per * n));
+    double *dA = dm, *dB = dA + inA * n, *dC = dB + inB * n, *dO = dC + inC * n;
+    int rc = 0;
+    const auto up = [&](double* dst, const double* src, size_t k) {
+        if (k && !rc && hipMemcpy(dst, src, sizeof(double) * k * n, hipMemcpyHostToDevice) != hipSuccess) rc = -2;
+    };
+    up(dA, a, inA);
+    up(dB, b, inB);
+    up(dC, c, inC);
+    if (!rc) {
+        hipLaunchKernelGGL(k_unit_sim3, dim3(ess_nblk(n, 256)), dim3(256), 0, 0, op, n, (const double*)dA,
+                           (const double*)dB, (const double*)dC, dO);
+        if (hipGetLastError() != hipSuccess || hipMemcpy(out, dO, sizeof(double) * nOut * n, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = -2;
+    }
+    (void)hipFree(dm);
+    return rc;
 }
 
 }  // namespace orbgpu

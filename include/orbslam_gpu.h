@@ -965,6 +965,37 @@ int orbgpu_unit_set_posegraph_check(int on);
  * height (0 = a single leaf). */
 int orbgpu_unit_nd_order(int n, const int32_t* adjStart, const int32_t* adj, int leaf, int32_t* perm,
                          int32_t* n_nodes, int32_t* height);
+/* The Sim3 arithmetic the Sim3 engines share (csrc/sim3_math.hpp) and EdgeSim3::computeError, one
+ * thread per item through the engines' own inline functions.  Sim3 rows are 8 doubles (q xyzw, t,
+ * s).  op 0: exp, a n x 7 -> out n x 8; 1: log, a n x 8 -> n x 7; 2: a * b -> n x 8; 3: a^-1 ->
+ * n x 8; 4: a.map(b), b n x 3 -> n x 3; 5: log(a * b * c^-1) (a = the measurement, b = S_i,
+ * c = S_j) -> n x 7.  Unused inputs may be NULL. */
+int orbgpu_unit_sim3(int op, int n, const double* a, const double* b, const double* c, double* out);
+/* One linearisation and one LM trial of Optimizer_OptimizeEssentialGraph at a given lambda,
+ * through the engine's own launches.  Every pointer may be NULL (skipped).  With no edge or no
+ * system vertex only nV, sysIdx, meas and the full pass are written and solver = -1. */
+typedef struct essgraph_stage {
+    int solver;           /* out: 0 dense, 1 tiled (block-sparse, groups of 7 rows) */
+    int nV;               /* out: system vertices (free, with an edge); n = 7 nV rows */
+    int ok;               /* out: the factorisation met no zero pivot */
+    int32_t* sysIdx;      /* nKF: system index, -1 outside the system */
+    double* meas;         /* nE x 8 */
+    double* err;          /* nE x 7: errors at the linearisation point */
+    double* chi2e;        /* nE */
+    double* J;            /* nE x 98: [side][row k][column d] */
+    double* H;            /* n x n: upper triangle in system order as the solver's storage holds it
+                             after the assembly (lambda added), lower triangle 0 */
+    double* b;            /* n */
+    double* x_solve;      /* n: the solver's x */
+    double* x;            /* n: x after the update kernel (scale entries zeroed under bFixScale) */
+    double* est_trial;    /* nKF x 8: the trial's estimates */
+    double* chi2e_trial;  /* nE */
+    double chi2, chi2_trial, scale; /* out: canonical sums (scale without computeScale's 1e-3) */
+} essgraph_stage;
+int orbgpu_unit_essgraph_stage(const essgraph_problem* P, double lambda, essgraph_stage* out);
+/* Test knob: the pose graph's dense single-workgroup solver takes systems of at most `rows` rows
+ * (default and maximum 144); 0 sends every system to the block-sparse solver.  Process-wide. */
+int orbgpu_unit_set_ess_dense_max(int rows);
 /* Instrumented builds only (make prof): read and clear the BA/pose section timers (32 x u64
  * clock64 deltas of workgroup 0); ORB_E_INVALID in normal builds. */
 int orbgpu_debug_prof(unsigned long long* out32);

@@ -224,6 +224,25 @@ def edge_errors(M, Si, Sj, assoc, A=MatrixAlgebra):
     return A.log(A.mul(M, A.mul(Si, A.inv(Sj))))
 
 
+def numeric_jacobian(M, est, ei, ej, fix, assoc=0, A=MatrixAlgebra):
+    """g2o's central differences (delta 1e-9) of every edge by both of its vertices, fixed ones
+    included: J[side, e, k, d]"""
+    J = np.zeros((2, len(ei), 7, 7))
+    for side, idx in ((0, ei), (1, ej)):
+        for d in range(7):
+            ev = []
+            for sgn in (1.0, -1.0):
+                add = np.zeros(7)
+                add[d] = sgn * DELTA
+                if fix:
+                    add[6] = 0
+                P = A.mul(A.exp(add), take(est, idx))
+                Si, Sj = (P, take(est, ej)) if side == 0 else (take(est, ei), P)
+                ev.append(edge_errors(M, Si, Sj, assoc, A))
+            J[side, :, :, d] = (ev[0] - ev[1]) / (2 * DELTA)
+    return J
+
+
 VARIANTS = ("natural_cholesky", "reversed_lu", "assoc", "quaternion")
 
 
@@ -261,19 +280,7 @@ def ref_optimize(problem, nIterations=20, variant=0):
         order = range(nE - 1, -1, -1) if variant == 1 else range(nE)
         for _ in range(nIterations):
             err = errors(est)
-            J = np.zeros((2, nE, 7, 7))
-            for side, idx in ((0, ei), (1, ej)):
-                for d in range(7):
-                    ev = []
-                    for sgn in (1.0, -1.0):
-                        add = np.zeros(7)
-                        add[d] = sgn * DELTA
-                        if fix:
-                            add[6] = 0
-                        P = A.mul(A.exp(add), take(est, idx))
-                        Si, Sj = (P, take(est, ej)) if side == 0 else (take(est, ei), P)
-                        ev.append(edge_errors(M, Si, Sj, assoc, A))
-                    J[side, :, :, d] = (ev[0] - ev[1]) / (2 * DELTA)
+            J = numeric_jacobian(M, est, ei, ej, fix, assoc, A)
             H, b = np.zeros((n, n)), np.zeros(n)
             for e in order:
                 a, c = sys_idx[ei[e]], sys_idx[ej[e]]
@@ -512,3 +519,198 @@ def variant_spread(refs):
     c1 = np.array([r["chi2"][-1] for r in refs])
     pose = max(pose_distance(refs[a]["Scw"], refs[b]["Scw"]) for a in range(len(refs)) for b in range(a))
     return (c0.max() - c0.min()) / c0.max(), (c1.max() - c1.min()) / c1.max(), pose
+
+
+# ---------------------------------------------------------------- graphs of the stage tests
+def flip_edges(pr, seed):
+    """The same graph with the direction of a seeded half of the edges reversed.  The call derives
+    each measurement Sji from the tables, so a reversed edge is as consistent as the original."""
+    rng = np.random.default_rng(seed)
+    nE = len(pr["edge_i"])
+    swap = np.zeros(nE, bool)
+    swap[rng.permutation(nE)[:nE // 2]] = True
+    out = dict(pr)
+    out["edge_i"] = np.where(swap, pr["edge_j"], pr["edge_i"]).astype(np.int32)
+    out["edge_j"] = np.where(swap, pr["edge_i"], pr["edge_j"]).astype(np.int32)
+    return out
+
+
+def system_index(pr):
+    """sysIdx (free vertices with an edge, in the caller's order; -1 otherwise) and their count"""
+    nKF = len(pr["fixed"])
+    has = np.zeros(nKF, bool)
+    has[pr["edge_i"]] = True
+    has[pr["edge_j"]] = True
+    sys_idx = -np.ones(nKF, np.int32)
+    free = np.flatnonzero(~np.asarray(pr["fixed"]).astype(bool) & has)
+    sys_idx[free] = np.arange(len(free))
+    return sys_idx, len(free)
+
+
+def edge_orders(pr):
+    """(edges with both ends in the system and sysIdx[i] < sysIdx[j], with sysIdx[i] > sysIdx[j])"""
+    s, _ = system_index(pr)
+    a, b = s[pr["edge_i"]], s[pr["edge_j"]]
+    both = (a >= 0) & (b >= 0)
+    return int((both & (a < b)).sum()), int((both & (a > b)).sum())
+
+
+def _append_edges(pr, pairs):
+    out = dict(pr)
+    out["edge_i"] = np.concatenate([pr["edge_i"], [p[0] for p in pairs]]).astype(np.int32)
+    out["edge_j"] = np.concatenate([pr["edge_j"], [p[1] for p in pairs]]).astype(np.int32)
+    out["edge_loop"] = np.concatenate([pr["edge_loop"], np.zeros(len(pairs), np.uint8)])
+    return out
+
+
+def perturbed_graph(N, edges, fixed, seed, fix_scale):
+    """Measurements from a ground truth on the circle (in ScwNonCorrected; every edge a normal edge),
+    estimates perturbed by (0.02, 0.1, 0.02) in (rotation, translation, log scale): every edge has a
+    residual of that size.  Vectorised: for graphs of a thousand keyframes."""
+    rng = np.random.default_rng(seed)
+    R, t, s = _truth(N)
+    if not fix_scale:
+        s = np.exp(0.05 * rng.standard_normal(N))
+    G = (R, t, s)
+    u = np.concatenate([0.02 * rng.standard_normal((N, 3)), 0.1 * rng.standard_normal((N, 3)),
+                        (0.0 if fix_scale else 0.02) * rng.standard_normal((N, 1))], -1)
+    fx = np.zeros(N, np.uint8)
+    fx[list(fixed)] = 1
+    return dict(Scw=sim3_to_rows(mul(s3_exp(u), G)), ScwNonCorrected=sim3_to_rows(G), fixed=fx,
+                edge_i=np.array([e[0] for e in edges], np.int32), edge_j=np.array([e[1] for e in edges], np.int32),
+                edge_loop=np.zeros(len(edges), np.uint8), bFixScale=int(fix_scale))
+
+
+def _band(N):
+    return [(i, i - k) for i in range(1, N) for k in (1, 2, 3) if i - k >= 0]
+
+
+@functools.lru_cache(maxsize=None)
+def stage_graph(name):
+    """The graphs of test_gpu_essgraph_stages.py (do not modify); every one has edges in both
+    directions of the system order.
+      g1_free / g1_fix   the n12 rings, 77 rows
+      ring20 / ring21    rings with 20 / 21 free vertices: 140 and 147 rows, the two sides of the
+                         dense solver's limit of 144
+      hub                80 keyframes (scale fixed), vertex 5 joined to every vertex the ring does not join it to,
+                         five of those pairs twice: degree above 64, 553 rows
+      split              two rings of 13 keyframes with a fixed vertex each and no edge between them,
+                         one free vertex of the second joined to fixed vertices only, and between the
+                         two an edge-less free vertex (a gap in sysIdx): 27 keyframes, 168 rows
+      few_free           1,370 keyframes, five of them free, the band's edge list cut to 4,097
+      e1 / e63 / e64     one free vertex and one edge; nine free (63 rows) and 63 edges; five and 64
+      e65                a chain of 65 edges with 64 free vertices: 448 rows
+      big                586 free vertices in a band: 4,102 rows"""
+    if name in ("g1_free", "g1_fix"):
+        return flip_edges(ring_case("n12_free" if name == "g1_free" else "n12_fix"), 11)
+    if name in ("ring20", "ring21"):
+        N = 21 if name == "ring20" else 22
+        return flip_edges(ring_graph(N=N, seed=9, rot_sigma=0.03, trans_sigma=0.1, scale_sigma=0.04, fix_scale=False), 12)
+    if name == "hub":
+        # scale fixed: with it free the reference's own rounding variants end 3e-2 apart here (ten
+        # rejected trials in the theta ~ 0, sigma != 0 arm of exp, see ZERO_SEEDS); fixed they agree to 4e-6
+        pr = ring_graph(N=80, seed=4, rot_sigma=0.01, trans_sigma=0.05, scale_sigma=0.01, fix_scale=True)
+        joined = {frozenset(p) for p in zip(pr["edge_i"].tolist(), pr["edge_j"].tolist())}
+        spokes = [(v, 5) for v in range(80) if v != 5 and frozenset((v, 5)) not in joined]
+        return flip_edges(_append_edges(pr, spokes + spokes[10:15]), 13)
+    if name == "split":
+        a = ring_graph(N=13, seed=21, rot_sigma=0.03, trans_sigma=0.1, scale_sigma=0.04, fix_scale=False)
+        b = ring_graph(N=13, seed=22, rot_sigma=0.03, trans_sigma=0.1, scale_sigma=0.04, fix_scale=False)
+        keep = (b["edge_i"] != 6) & (b["edge_j"] != 6)   # vertex 6 of the second ring keeps no edge to a free vertex
+        lone = a["Scw"][4:5].copy()
+        lone[0, 4:7] += 2.0
+        pr = dict(Scw=np.concatenate([a["Scw"], lone, b["Scw"]]),
+                  ScwNonCorrected=np.concatenate([a["ScwNonCorrected"], lone, b["ScwNonCorrected"]]),
+                  fixed=np.concatenate([a["fixed"], [0], b["fixed"]]).astype(np.uint8),
+                  edge_i=np.concatenate([a["edge_i"], b["edge_i"][keep] + 14]).astype(np.int32),
+                  edge_j=np.concatenate([a["edge_j"], b["edge_j"][keep] + 14]).astype(np.int32),
+                  edge_loop=np.concatenate([a["edge_loop"], b["edge_loop"][keep]]), bFixScale=0)
+        Scw = pr["Scw"].copy()
+        Scw[20, 4:7] += 0.05   # a residual on that vertex's edges (its tables agree otherwise)
+        pr["Scw"] = Scw
+        return flip_edges(_append_edges(pr, [(20, 14), (14, 20), (20, 0)]), 14)
+    if name == "few_free":
+        return flip_edges(perturbed_graph(1370, _band(1370)[:4097], set(range(1370)) - {40, 41, 42, 43, 900}, 31, False), 15)
+    if name == "e1":
+        return perturbed_graph(30, [(7, 6)], set(range(30)) - {7}, 32, False)
+    if name == "e63":
+        return flip_edges(perturbed_graph(30, _band(30)[:63], set(range(30)) - set(range(2, 11)), 33, False), 16)
+    if name == "e64":
+        return flip_edges(perturbed_graph(30, _band(30)[:64], set(range(30)) - {3, 4, 5, 6, 15}, 34, False), 17)
+    if name == "e65":
+        return flip_edges(perturbed_graph(66, [(i, i - 1) for i in range(1, 66)], {0, 1}, 35, False), 18)
+    if name == "big":
+        return flip_edges(perturbed_graph(587, _band(587), {0}, 36, False), 19)
+    raise KeyError(name)
+
+
+STAGE_GRAPHS = ("g1_free", "g1_fix", "ring20", "ring21", "hub", "split", "few_free", "e1", "e63", "e64", "e65", "big")
+
+
+def gather_lists(ei, ej, sys_idx, nV, flip_side_when_a_below_b=False):
+    """{(a, b), a <= b in system order: [(edge, side of a)] in edge order} from the edge list alone
+    (the deliberate error: the side bit of the a < b entries flipped)"""
+    lists = {}
+    for e in range(len(ei)):
+        a, b = int(sys_idx[ei[e]]), int(sys_idx[ej[e]])
+        if a >= 0:
+            lists.setdefault((a, a), []).append((e, 0))
+        if b >= 0:
+            lists.setdefault((b, b), []).append((e, 1))
+        if a >= 0 and b >= 0:
+            if a < b:
+                lists.setdefault((a, b), []).append((e, 1 if flip_side_when_a_below_b else 0))
+            else:
+                lists.setdefault((b, a), []).append((e, 1))
+    return lists
+
+
+def assemble_f64(J, err, ei, ej, sys_idx, nV, lam, want_H=True, flip_side_when_a_below_b=False):
+    """k_ess_assemble in float64, operation for operation: per entry h = sum over k = 0..6 of
+    Ja[k][r] Jb[k][c] in that order, acc += h over the pair's entries in edge order, + lambda on the
+    diagonal; b: g = sum over k of Ja[k][r] e[k], acc -= g.  J: nE x 2 x 7 x 7 ([side][k][d]); only
+    blocks of system vertices are read.  -> (H upper triangle, lower zero; or None), b"""
+    n = 7 * nV
+    H = np.zeros((n, n)) if want_H else None
+    bv = np.zeros(n)
+    for (a, b), ents in gather_lists(ei, ej, sys_idx, nV, flip_side_when_a_below_b).items():
+        if a == b:
+            g_acc = np.zeros(7)
+            for e, s in ents:
+                g = np.zeros(7)
+                for k in range(7):
+                    g = g + J[e, s, k, :] * err[e, k]
+                g_acc = g_acc - g
+            bv[7 * a:7 * a + 7] = g_acc
+        if not want_H:
+            continue
+        acc = np.zeros((7, 7))
+        for e, s in ents:
+            Ja, Jb = J[e, s], J[e, s if a == b else 1 - s]
+            h = np.zeros((7, 7))
+            for k in range(7):
+                h = h + np.outer(Ja[k], Jb[k])
+            acc = acc + h
+        if a == b:
+            acc[np.diag_indices(7)] += lam
+            acc = np.triu(acc)
+        H[7 * a:7 * a + 7, 7 * b:7 * b + 7] = acc
+    return H, bv
+
+
+def csum(v):
+    """ora_csum (oracle/ba.c): chunks of 64, each by the tree a[i] += a[i + off], off = 32 .. 1, zero
+    padded; recursively over the chunk totals; a single term is returned untouched"""
+    v = np.array(v, np.float64)
+    if len(v) == 0:
+        return 0.0
+    while len(v) > 1:
+        m = (len(v) + 63) // 64
+        a = np.zeros((m, 64))
+        a.reshape(-1)[:len(v)] = v
+        off = 32
+        while off >= 1:
+            a[:, :off] = a[:, :off] + a[:, off:2 * off]
+            off >>= 1
+        v = a[:, 0].copy()
+    return float(v[0])
