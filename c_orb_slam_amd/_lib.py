@@ -69,6 +69,19 @@ class orb_localprep(C.Structure):
                 ("row", C.c_void_p), ("skip", C.c_void_p)]
 
 
+class orb_triangulate(C.Structure):
+    _fields_ = [("KF2", C.POINTER(orb_frame)), ("depth2", C.c_void_p), ("levelSigma2_2", C.c_void_p),
+                ("npairs", C.c_int), ("pairs", C.c_void_p), ("x3D", C.c_void_p), ("status", C.c_void_p),
+                ("normal", C.c_void_p), ("max_dist", C.c_void_p), ("min_dist", C.c_void_p)]
+
+
+class orb_pointupdate(C.Structure):
+    _fields_ = [("npts", C.c_int), ("obs_start", C.c_void_p), ("obs_desc", C.c_void_p), ("best", C.c_void_p),
+                ("pos", C.c_void_p), ("obs_Ow", C.c_void_p), ("ref_Ow", C.c_void_p), ("ref_scale", C.c_void_p),
+                ("ref_scale_top", C.c_void_p), ("normal", C.c_void_p), ("max_dist", C.c_void_p),
+                ("min_dist", C.c_void_p)]
+
+
 class orb_localmap(C.Structure):
     _fields_ = [("n", C.c_int), ("pos", C.c_void_p), ("desc", C.c_void_p), ("observations", C.c_void_p),
                 ("max_dist", C.c_void_p), ("min_dist", C.c_void_p), ("normal", C.c_void_p), ("skip", C.c_void_p)]
@@ -173,6 +186,8 @@ def lib():
                                        P(i32)]
     L.ORBmatcher_SearchBySim3.argtypes = [vp, P(orb_frame), vp, P(orb_frame), vp, P(orb_mappoints),
                                           P(orb_mappoint_geo), vp, f32, vp, vp, f32, f32, vp, P(i32)]
+    L.LocalMapping_CreateNewMapPoints_batch.argtypes = [vp, P(orb_frame), vp, vp, f32, i32, vp]
+    L.MapPoint_Update_batch.argtypes = [vp, P(orb_pointupdate)]
     L.ORBmatcher_SearchCandidates.argtypes = [vp, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]
     L.orb_rng_seed.argtypes = [vp, C.c_uint]
     L.orb_rng_rand.argtypes = [vp]

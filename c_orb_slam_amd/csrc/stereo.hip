@@ -352,16 +352,11 @@ __global__ void __launch_bounds__(256) k_unproject(UnprojBatch B) {
     if (P.mp) P.mp[i] = z > 0 ? P.mp_base + i : -1;
     if (!(z > 0)) return;
     const orb_kp_dev kp = P.keys[i];
-    const float x = (kp.x - P.cx) * z * P.invfx;
-    const float y = (kp.y - P.cy) * z * P.invfy;
     const float* T = P.Twc;
     float X[3];
+    unproject_point(T, kp.x, kp.y, z, P.cx, P.cy, P.invfx, P.invfy, X);
 #pragma unroll
-    for (int r = 0; r < 3; r++) {
-        const double acc = (double)T[r * 4 + 0] * x + (double)T[r * 4 + 1] * y + (double)T[r * 4 + 2] * z;
-        X[r] = (float)(acc + (double)T[r * 4 + 3]);
-        P.x3D[3 * i + r] = X[r];
-    }
+    for (int r = 0; r < 3; r++) P.x3D[3 * i + r] = X[r];
     if (P.normal) {
         // MapPoint::UpdateNormalAndDepth with the creating frame as the only observation
         // (MapPoint.cc:331-371): cv::norm accumulated in double, normali / norm as a float

@@ -75,6 +75,21 @@ struct LocalPrepDev {
     uint8_t* skip;
 };
 int local_prep_batch(const LocalPrepDev* d_probs, int count, hipStream_t s);
+// Frame::UnprojectStereo for one keypoint (Frame.cc:666-680): x3Dc = ((u-cx)*z*invfx,
+// (v-cy)*z*invfy, z) in float, then mRwc*x3Dc + mOw as one cv::gemm (f64 accumulation, one
+// rounding to float).  T = [mRwc | mOw], rows of 4.  Shared by k_unproject and
+// LocalMapping::CreateNewMapPoints' stereo branch (localmap.hip).
+__device__ __forceinline__ void unproject_point(const float* T, float u, float v, float z, float cx, float cy,
+                                                float invfx, float invfy, float (&X)[3]) {
+    const float x = (u - cx) * z * invfx;
+    const float y = (v - cy) * z * invfy;
+#pragma unroll
+    for (int r = 0; r < 3; r++) {
+        const double acc = (double)T[r * 4 + 0] * x + (double)T[r * 4 + 1] * y + (double)T[r * 4 + 2] * z;
+        X[r] = (float)(acc + (double)T[r * 4 + 3]);
+    }
+}
+
 constexpr int kUnprojPerLaunch = 56;   // frames per launch, passed by value (kernel-argument space)
 // enqueue on `s` (no staging buffer: the frames are kernel arguments)
 int unproject_batch(const UnprojDev* probs, int count, hipStream_t s);

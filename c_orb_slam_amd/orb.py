@@ -648,6 +648,68 @@ class ORBmatcher:
                                                         ptr(pairs), cap, C.byref(n)), "SearchForTriangulation")
         return pairs[:n.value].copy()
 
+    def CreateNewMapPoints(self, KF1: Frame, depth1, sigma2_1, scaleFactor, neighbours, want_normal=True):
+        """LocalMapping::CreateNewMapPoints' geometry (LocalMapping.cc:262-437) for the current
+        keyframe and all its neighbours in one launch.  neighbours: [(KF2, depth2, sigma2_2, pairs), ...]
+        with pairs (n, 2) of (idx1, idx2) as SearchForTriangulation returns them; depth is mvDepth
+        or None for a monocular keyframe.  -> [(x3D, status, normal, max_dist, min_dist), ...];
+        rows with status <= 0 stay zero."""
+        from ._lib import orb_triangulate
+        d1 = None if depth1 is None else np.ascontiguousarray(depth1, np.float32)
+        s1 = np.ascontiguousarray(sigma2_1, np.float32)
+        k1 = KF1.cstruct()
+        keep, outs = [k1], []
+        arr = (orb_triangulate * max(len(neighbours), 1))()
+        for j, (KF2, depth2, sigma2_2, pairs) in enumerate(neighbours):
+            k2 = KF2.cstruct()
+            d2 = None if depth2 is None else np.ascontiguousarray(depth2, np.float32)
+            s2 = np.ascontiguousarray(sigma2_2, np.float32)
+            pr = np.ascontiguousarray(pairs, np.int32).reshape(-1, 2)
+            n = len(pr)
+            x3D, status = np.zeros((n, 3), np.float32), np.zeros(n, np.int8)
+            normal, mx, mn = np.zeros((n, 3), np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+            keep += [k2, d2, s2, pr]
+            q = arr[j]
+            q.KF2 = C.pointer(k2)
+            q.depth2, q.levelSigma2_2, q.npairs = ptr(d2), ptr(s2), n
+            q.pairs, q.x3D, q.status = ptr(pr), ptr(x3D), ptr(status)
+            if want_normal:
+                q.normal, q.max_dist, q.min_dist = ptr(normal), ptr(mx), ptr(mn)
+            outs.append((x3D, status, normal, mx, mn))
+        check(self._L.LocalMapping_CreateNewMapPoints_batch(self._h, C.byref(k1), ptr(d1), ptr(s1),
+                                                            float(scaleFactor), len(neighbours), arr),
+              "LocalMapping_CreateNewMapPoints_batch")
+        return outs
+
+    def UpdateMapPoints(self, obs_start, obs_desc=None, pos=None, obs_Ow=None, ref_Ow=None, ref_scale=None,
+                        ref_scale_top=None):
+        """MapPoint::ComputeDistinctiveDescriptors (MapPoint.cc:242-307, with obs_desc) and
+        MapPoint::UpdateNormalAndDepth (MapPoint.cc:331-371, with pos) for a batch of map points
+        whose observations are the CSR obs_start.  -> dict with `best` and / or `normal`,
+        `max_dist`, `min_dist`; rows of points without observations stay zero (best: -1)."""
+        from ._lib import orb_pointupdate
+        st = np.ascontiguousarray(obs_start, np.int32)
+        n = len(st) - 1
+        U = orb_pointupdate()
+        U.npts, U.obs_start = n, ptr(st)
+        out, keep = {}, [st]
+        if obs_desc is not None:
+            d = np.ascontiguousarray(obs_desc, np.uint8).reshape(-1, 32)
+            best = np.full(max(n, 1), -1, np.int32)
+            keep.append(d)
+            U.obs_desc, U.best = ptr(d), ptr(best)
+            out["best"] = best[:n]
+        if pos is not None:
+            arrs = [np.ascontiguousarray(a, np.float32) for a in (pos, obs_Ow, ref_Ow, ref_scale, ref_scale_top)]
+            keep += arrs
+            normal = np.zeros((max(n, 1), 3), np.float32)
+            mx, mn = np.zeros(max(n, 1), np.float32), np.zeros(max(n, 1), np.float32)
+            U.pos, U.obs_Ow, U.ref_Ow, U.ref_scale, U.ref_scale_top = (ptr(a) for a in arrs)
+            U.normal, U.max_dist, U.min_dist = ptr(normal), ptr(mx), ptr(mn)
+            out.update(normal=normal[:n], max_dist=mx[:n], min_dist=mn[:n])
+        check(self._L.MapPoint_Update_batch(self._h, C.byref(U)), "MapPoint_Update_batch")
+        return out
+
     def SearchCandidates(self, qdesc, tdesc, offsets, cand):
         q = np.ascontiguousarray(qdesc, np.uint8).reshape(-1, 32)
         t = np.ascontiguousarray(tdesc, np.uint8).reshape(-1, 32)

@@ -539,6 +539,80 @@ int ORBmatcher_SearchBySim3(ORBmatcher_h h, const orb_frame* KF1, const int32_t*
                             const uint8_t* bad, float s12, const float* R12, const float* t12,
                             float logScaleFactor, float th, int32_t* matches12, int* nfound);
 
+/* ---- LocalMapping: point creation and map-point updates ---------------------------------
+ * Host pointers only (ORB_E_INVALID in device-pointer mode).  Both calls run on
+ * ORBmatcher_stream(h) and return after their results are on the host; each packs its inputs
+ * into one upload and fetches its results in one download.  Arguments are validated before
+ * the device is touched; the handle is looked at last, so a malformed call answers
+ * ORB_E_INVALID and a well-formed call with h == NULL answers ORB_E_NODEVICE where no device
+ * is visible (ORB_E_INVALID otherwise). */
+
+/* void LocalMapping::CreateNewMapPoints()                         LocalMapping.cc:207-452
+ * The geometry applied to every pair SearchForTriangulation returns (262-437), for the
+ * current keyframe KF1 (mpCurrentKeyFrame) and `count` neighbours, in one kernel launch with
+ * one thread per pair.  Per pair: the parallax of the two rays and of the stereo
+ * baseline (only the first stereo keypoint's is evaluated: `if / else if`), then
+ *   cosParallaxRays < cosParallaxStereo && > 0 && (stereo1 || stereo2 || < 0.9998):
+ *       linear triangulation, cv::SVD::compute of the 4x4 float A      status 1
+ *   else stereo1 && cosParallaxStereo1 < cosParallaxStereo2: UnprojectStereo(idx1) of KF1  2
+ *   else stereo2 && cosParallaxStereo2 < cosParallaxStereo1: UnprojectStereo(idx2) of KF2  3
+ *   else                                                                          status 0
+ * and the tests in the reference's order: homogeneous w == 0 (-1), z1 <= 0 (-2),
+ * z2 <= 0 (-4), reprojection error in KF1 (-3: chi2 5.991 monocular, 7.8
+ * stereo) and in KF2 (-5), a zero distance to a camera centre (-6), scale
+ * consistency against ratioFactor = 1.5f * scaleFactor (-7).  A pair with status <= 0
+ * leaves its x3D / normal / max_dist / min_dist rows untouched.
+ * normal / max_dist / min_dist (all three or none): MapPoint::UpdateNormalAndDepth
+ * (MapPoint.cc:331-371) of the new point, observations {KF1, KF2}, reference keyframe KF1.
+ * The neighbour gates (baseline < mb; baseline / median depth < 0.01) and ComputeF12
+ * stay with the caller.  cv::SVD and the float libm calls are restated.
+ * KF1 / KF2 fields read: N, keysUn (pt, octave), uRight (NULL = monocular keyframe), Tcw,
+ * fx fy cx cy bf b, scaleFactors, nlevels.  depth (mvDepth, N) is required with uRight.
+ * ORB_E_INVALID: a null pointer, a negative count, a pair index outside [0, N), an octave
+ * outside [0, nlevels). */
+typedef struct orb_triangulate {   /* one neighbour keyframe pKF2 */
+    const orb_frame* KF2;
+    const float* depth2;           /* pKF2->mvDepth (KF2->N) or NULL (monocular) */
+    const float* levelSigma2_2;    /* pKF2->mvLevelSigma2 (nlevels) */
+    int npairs;
+    const int32_t* pairs;          /* npairs x 2 (idx1, idx2): ORBmatcher_SearchForTriangulation's output */
+    float* x3D;                    /* out: npairs x 3 */
+    int8_t* status;                /* out: npairs */
+    float* normal;                 /* out, optional: npairs x 3 */
+    float* max_dist;               /* out, optional: npairs */
+    float* min_dist;               /* out, optional: npairs */
+} orb_triangulate;
+int LocalMapping_CreateNewMapPoints_batch(ORBmatcher_h h, const orb_frame* KF1, const float* depth1,
+                                          const float* levelSigma2_1, float scaleFactor, int count,
+                                          const orb_triangulate* nb);
+
+/* void MapPoint::ComputeDistinctiveDescriptors()                  MapPoint.cc:242-307
+ * void MapPoint::UpdateNormalAndDepth()                           MapPoint.cc:331-371
+ * for npts map points at once (LocalMapping::ProcessNewKeyFrame, the new points of CreateNewMapPoints,
+ * LocalMapping.cc:543-552 after Fuse, and after a loop correction).  Observations are a CSR in
+ * mObservations order with bad keyframes already dropped; obs_start[0] == 0 and non-decreasing.
+ * Descriptor part (obs_desc != NULL): best[p] = the index, within point p's own observations,
+ * of the descriptor with the least median Hamming distance to all of them (the median is
+ * sorted(D[i][.])[0.5 * (k - 1)], self distance included; the first index wins a tie), -1 for a
+ * point without observations.  Normal part (pos != NULL): normal = sum_i (pos - Ow_i) / |pos -
+ * Ow_i| in the given order, divided by the count; max_dist = |pos - ref_Ow| * ref_scale,
+ * min_dist = max_dist / ref_scale_top; rows of points without observations are untouched. */
+typedef struct orb_pointupdate {
+    int npts;
+    const int32_t* obs_start;      /* npts + 1 */
+    const uint8_t* obs_desc;       /* total x 32: pKF->mDescriptors.row(idx), or NULL */
+    int32_t* best;                 /* out: npts */
+    const float* pos;              /* npts x 3 (mWorldPos), or NULL */
+    const float* obs_Ow;           /* total x 3: pKF->GetCameraCenter() */
+    const float* ref_Ow;           /* npts x 3: mpRefKF->GetCameraCenter() */
+    const float* ref_scale;        /* npts: mpRefKF->mvScaleFactors[octave of the point's keypoint in mpRefKF] */
+    const float* ref_scale_top;    /* npts: mpRefKF->mvScaleFactors[nLevels-1] */
+    float* normal;                 /* out: npts x 3 */
+    float* max_dist;               /* out: npts */
+    float* min_dist;               /* out: npts */
+} orb_pointupdate;
+int MapPoint_Update_batch(ORBmatcher_h h, const orb_pointupdate* U);
+
 /* Hamming distances for CSR candidate lists (the inner loop of every Search*):
  * query q (descriptor qdesc[q]) against train rows cand[off[q] .. off[q+1]).
  * Writes dist[k] for every candidate k (dist may be NULL: best/second only) and best/second
