@@ -136,4 +136,9 @@ int ORBextractor_last_corner_count(ORBextractor_h h, long long* total) {
     return h->ex->corner_total(total) ? ORB_E_INVALID : ORB_OK;
 }
 
+int orbgpu_debug_extract_plan(ORBextractor_h h, int* flags, int* chain_from, int* tile_rows) {
+    if (!h) return ORB_E_INVALID;
+    return h->ex->last_plan(flags, chain_from, tile_rows) ? ORB_E_INVALID : ORB_OK;
+}
+
 }  // extern "C"

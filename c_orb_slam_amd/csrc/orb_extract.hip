@@ -896,7 +896,10 @@ __global__ void __launch_bounds__(256) k_orient_desc(const uint8_t* __restrict__
     }
     if (img >= B) return;
     const int k = grp * 4 + wv;
-    if (k >= nout[img] || k >= cap_per_image) return;   // wave-uniform: no barrier below
+    // an image with more keypoints than `cap` (or the selection capacity) has no selected list:
+    // k_sel_build reported it and wrote nothing, so sel holds an earlier call's entries
+    const int n = nout[img];
+    if (k >= n || n > cap_per_image || n > selcap) return;   // wave-uniform: no barrier below
     const int2 s = sel[(size_t)img * selcap + k];
     const uint32_t pk = (uint32_t)__builtin_amdgcn_readfirstlane(s.x);
     const int meta = __builtin_amdgcn_readfirstlane(s.y);
@@ -1405,6 +1408,10 @@ FlowArgs Extractor::flow_args(int v, int B) const {
 int Extractor::setup_geometry(int W, int H) {
     if (W == geomW_ && H == geomH_) return 0;
     if (W > 4000 || H > 4000) return -1;
+    // the tables below are rebuilt in place: until this call succeeds no geometry holds (a refused
+    // size must not leave its half-built tables behind the previous size's device buffers)
+    geomW_ = geomH_ = -1;
+    last_B_ = 0;
     levels_.assign(nlevels_, LevelHost{});
     size_t off = 0;
     for (int l = 0; l < nlevels_; l++) {
@@ -1791,6 +1798,8 @@ int Extractor::extract(const uint8_t* imgs, int B, int W, int H, int step, size_
     const int ncells = (int)cells_.size();
     if (work_B_ != B && build_work(B)) return -2;
     const bool split = fastSplit_ && work_part_[0] > 0 && work_part_[1] > 0;
+    int planFlags = (split ? kPlanFastSplit : 0) | (evBlur_ ? kPlanBlurSide : 0) | (B >= 8 ? kPlanTile32 : 0);
+    int planChainFrom = 0;
     // 1. pyramid; with the split, FAST of the levels below kFastSplitLevel starts on side_ as soon
     //    as they are built (their cells read nothing else), beside the small levels' chain
     {
@@ -1813,6 +1822,11 @@ int Extractor::extract(const uint8_t* imgs, int B, int W, int H, int step, size_
                                (uint8_t*)d_pyr_, img_bytes_, L0.pitch, L0.ph, d_gtotal_, (int*)d_nout_ + B);
         }
         const int lend = flow ? 1 : chain_ && !split ? chainFrom_ : nlevels_;   // levels [1, lend) one launch each
+        if (flow) planFlags |= kPlanFlow;
+        if (!flow && lend < nlevels_) {
+            planFlags |= kPlanChain;
+            planChainFrom = lend;
+        }
         for (int l = 1; l < lend; l++) {
             if (split && l == kFastSplitLevel) {
                 ORB_HIP_CHECK(hipEventRecord(evPyrA_, s));
@@ -1851,9 +1865,11 @@ int Extractor::extract(const uint8_t* imgs, int B, int W, int H, int step, size_
         const char* e = getenv("ORBGPU_BLUR_EARLY");
         return e && e[0] == '1';
     }();
-    if (blurEarly && !evBlur_)
+    if (blurEarly && !evBlur_) {
+        planFlags |= kPlanBlurEarly;
         hipLaunchKernelGGL(k_blur7, dim3(grid8((int)tiles_.size()), B), dim3(256), 0, s, (const uint8_t*)d_pyr_,
                            (uint8_t*)d_blur_, img_bytes_, blur_bytes_, (const BlurTile*)d_tiles_, (int)tiles_.size());
+    }
     if (evBlur_) {
         ORB_HIP_CHECK(hipStreamWaitEvent(side_, ev_[1], 0));
         hipLaunchKernelGGL(k_blur7, dim3(grid8((int)tiles_.size()), B), dim3(256), 0, side_, (const uint8_t*)d_pyr_,
@@ -1935,6 +1951,17 @@ int Extractor::extract(const uint8_t* imgs, int B, int W, int H, int step, size_
         ORB_HIP_CHECK(stream_wait(s));
     }
     last_B_ = B;
+    planFlags_ = planFlags;
+    planChainFrom_ = planChainFrom;
+    return 0;
+}
+
+int Extractor::last_plan(int* flags, int* chain_from, int* tile_rows) const {
+    if (last_B_ <= 0) return -1;
+    if (flags) *flags = planFlags_;
+    if (chain_from) *chain_from = planChainFrom_;
+    if (tile_rows)
+        for (int i = 0; i < 2 * nlevels_; i++) tile_rows[i] = ptile_th_[i];
     return 0;
 }
 

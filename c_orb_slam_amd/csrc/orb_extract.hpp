@@ -87,6 +87,10 @@ struct LevelArgs {
     LevelDev lv[kMaxLevels];
 };
 
+// Extractor::last_plan flags (orbgpu_debug_extract_plan)
+constexpr int kPlanFlow = 1, kPlanChain = 2, kPlanFastSplit = 4, kPlanBlurSide = 8, kPlanBlurEarly = 16,
+              kPlanTile32 = 32;
+
 struct LevelHost {
     int w, h, pw, ph, pitch, bpitch;
     size_t off, boff;
@@ -105,6 +109,9 @@ public:
     int get_blurred(int index, int level, uint8_t* dst, int dst_step, int* w, int* h);
     int timings(float* ms6);
     int corner_total(long long* total);   // FAST corners written by the last extract()
+    // which paths the last successful extract() launched (kPlan* bits), the first level of the
+    // chained pyramid (0: none) and the resize tile rows per variant and level (2 * nlevels ints)
+    int last_plan(int* flags, int* chain_from, int* tile_rows) const;
     hipStream_t stream() const { return stream_; }
     // recreate the stream with a CU mask leaving out one CU in every `one_in_n` (0: all CUs)
     int reserve_cus(int one_in_n);
@@ -170,6 +177,7 @@ private:
     size_t img_bytes_ = 0, blur_bytes_ = 0, slots_per_image_ = 0;
     int packed_cap_ = 0, sel_cap_ = 0;
     int last_B_ = 0;
+    int planFlags_ = 0, planChainFrom_ = 0;
 
     hipStream_t stream_ = nullptr;
     bool ownStream_ = true;

@@ -1077,6 +1077,16 @@ int orbgpu_debug_prof(unsigned long long* out32);
 int orbgpu_debug_prof_match(unsigned long long* out32);
 /* Section timers of the FAST cell kernel (instrumented builds only). */
 int orbgpu_debug_prof_extract(unsigned long long* out32);
+/* Test-only, read-only: what the last successful ORBextractor_extract* call of `h` launched.
+ * flags: 1 the pyramid as one launch of tasks (ORBGPU_PYR_FLOW), 2 the top levels chained in one
+ * launch (ORBGPU_PYR_CHAIN) from level *chain_from (0: none), 4 FAST split over two streams with
+ * both parts non-empty (ORBGPU_FAST_SPLIT), 8 the blur on the side stream (ORBGPU_BLUR_SIDE),
+ * 16 the blur right after the pyramid (ORBGPU_BLUR_EARLY), 32 the 32-row resize tile variant
+ * (batches of 8 or more).  tile_rows: 2 * nlevels ints, the resize tile height of the 16-row
+ * variant per level, then of the 32-row variant (less than 16 / 32 where the source rectangle of
+ * a full tile would not fit in LDS).  Every pointer may be NULL.  ORB_E_INVALID before the first
+ * successful call. */
+int orbgpu_debug_extract_plan(ORBextractor_h h, int* flags, int* chain_from, int* tile_rows);
 
 #ifdef __cplusplus
 }

@@ -16,16 +16,16 @@ pytestmark = pytest.mark.gpu
 KITTI_BF, KITTI_FX = 386.1448, 718.856
 
 
-def _pair(gpu, left, right, nfeat=1200, mbf=KITTI_BF, fx=KITTI_FX):
+def _pair(gpu, left, right, nfeat=1200, mbf=KITTI_BF, fx=KITTI_FX, sf=1.2, nl=8):
     h, w = left.shape
-    exL = gpu.ORBextractor(nfeat, 1.2, 8, 20, 7, max_width=w, max_height=h)
-    exR = gpu.ORBextractor(nfeat, 1.2, 8, 20, 7, max_width=w, max_height=h)
+    exL = gpu.ORBextractor(nfeat, sf, nl, 20, 7, max_width=w, max_height=h)
+    exR = gpu.ORBextractor(nfeat, sf, nl, 20, 7, max_width=w, max_height=h)
     kL, dL = exL(left)
     kR, dR = exR(right)
     m = gpu.ORBmatcher(0.6, True)
     mb = np.float32(np.float32(mbf) / np.float32(fx))
     uR, dep, n = m.ComputeStereoMatches(exL, exR, kL, dL, kR, dR, mbf, mb)
-    oL, oR = oracle_lib.OracleExtractor(nfeat, 1.2, 8, 20, 7), oracle_lib.OracleExtractor(nfeat, 1.2, 8, 20, 7)
+    oL, oR = oracle_lib.OracleExtractor(nfeat, sf, nl, 20, 7), oracle_lib.OracleExtractor(nfeat, sf, nl, 20, 7)
     okL, odL = oL(left)
     okR, odR = oR(right)
     assert np.array_equal(okL.view(np.uint8), kL.view(np.uint8)) and np.array_equal(okR.view(np.uint8), kR.view(np.uint8))
@@ -106,3 +106,51 @@ def test_stereo_one_extractor_batch(gpu):
     for b in range(P):
         assert np.array_equal(u1[b].view(np.uint32), u2[b].view(np.uint32))
         assert np.array_equal(d1[b].view(np.uint32), d2[b].view(np.uint32))
+
+
+# (W, H, scaleFactor, nlevels, nfeatures): small images on pyramids other than 1.2 x 8, so that
+# band = ceil(4 * scale[top]) + 3 and the per-level search run on other level tables
+SMALL_PYRAMIDS = [(330, 250, 2.0, 3, 400), (320, 240, 1.1, 12, 500), (400, 94, 1.2, 3, 300),
+                  (160, 120, 1.2, 4, 300), (333, 217, 1.5, 4, 400)]
+
+
+def _small_calib(w):
+    mbf, fx = KITTI_BF * w / 1241, KITTI_FX * w / 1241
+    return mbf, fx, np.float32(np.float32(mbf) / np.float32(fx))
+
+
+@pytest.mark.parametrize("w,h,sf,nl,nf", SMALL_PYRAMIDS)
+def test_stereo_small_pyramids(gpu, w, h, sf, nl, nf):
+    L, R = synthetic.stereo_batch(3, 1, w, h)
+    mbf, fx, _ = _small_calib(w)
+    (uR, dep, n), (ouR, odep, on), (kL, _) = _pair(gpu, L[0], R[0], nfeat=nf, mbf=mbf, fx=fx, sf=sf, nl=nl)
+    assert n == on
+    assert np.array_equal(uR.view(np.uint32), ouR.view(np.uint32))
+    assert np.array_equal(dep.view(np.uint32), odep.view(np.uint32))
+    assert n == int((uR >= 0).sum()) and n >= 20, n
+    assert len(set(kL["octave"][uR >= 0])) >= 2
+
+
+def test_stereo_small_pyramid_one_extractor(gpu):
+    """The one-extractor form (first_left / first_right) on a 333 x 217, 1.5 x 4 pyramid: lefts and
+    rights as one batch, every pair equal to the oracle's matches."""
+    w, h, sf, nl, nf = SMALL_PYRAMIDS[-1]
+    P = 2
+    Ls, Rs = synthetic.stereo_batch(3, P, w, h)
+    mbf, _, mb = _small_calib(w)
+    one = gpu.ORBextractor(nf, sf, nl, 20, 7, max_width=w, max_height=h, max_batch=2 * P)
+    kd = one.extract_batch(np.concatenate([Ls, Rs]))
+    m = gpu.ORBmatcher(0.6, True)
+    us, ds, ns = m.ComputeStereoMatches_batch(one, one, [k for k, _ in kd[:P]], [d for _, d in kd[:P]],
+                                              [k for k, _ in kd[P:]], [d for _, d in kd[P:]], mbf, mb,
+                                              first_left=0, first_right=P)
+    for b in range(P):
+        oL, oR = oracle_lib.OracleExtractor(nf, sf, nl, 20, 7), oracle_lib.OracleExtractor(nf, sf, nl, 20, 7)
+        okL, odL = oL(Ls[b])
+        okR, odR = oR(Rs[b])
+        assert np.array_equal(okL.view(np.uint8), kd[b][0].view(np.uint8))
+        assert np.array_equal(okR.view(np.uint8), kd[P + b][0].view(np.uint8))
+        ouR, odep, on = oracle_lib.oracle_stereo_matches(oL, oR, okL, odL, okR, odR, h, mbf, mb)
+        assert ns[b] == on and on >= 20, (b, ns[b], on)
+        assert np.array_equal(us[b].view(np.uint32), ouR.view(np.uint32)), b
+        assert np.array_equal(ds[b].view(np.uint32), odep.view(np.uint32)), b
