@@ -19,17 +19,36 @@
 // sign of a zero).  The forward solve y_i -= L[i][k] y_k runs k ascending, y_k /= d_k, the
 // backward solve y_i -= L[k][i] y_k k descending -- the same sequences whatever the schedule.
 //
-// Schedule: the tree's levels (height 0 = leaves) run bottom-up, two launches per level:
-//   update  one workgroup per target tile (I, J) of the level's nodes that a DESCENDANT tile
-//           row K touches: A(I, J) -= sum_K L(I, K) U(K, J), K ascending (left-looking: reads
-//           finished descendant tiles only, writes a tile owned by this node: no races);
-//   factor  the level's nodes walk their own panels right-looking in lock step: per panel step
-//           three launches over every node of the level (diagonal tiles, the panel rows' U/LT
-//           tiles, the trailing updates of the nodes' own rows), a workgroup per tile; then
-//           one wave per node solves its rows of L y = b;
-// then the backward solve runs the levels top-down (one wave per node).  Nodes of one level
-// share no tile, so their workgroups run concurrently; the descendants' updates of an
-// ancestor tile arrive in ascending K, i.e. in pivot order, as in the sequential sweep.
+// Schedule (SparseLdlt::solve): the tree's levels (height 0 = leaves) run bottom-up.  Per level:
+//   k_ldlt_update_q  left-looking: every target tile (I, J) of the level's nodes that a DESCENDANT
+//           tile row K touches receives A(I, J) -= sum_K L(I, K) U(K, J), K ascending (reads
+//           finished descendant tiles only, writes a tile owned by this node: no races); four
+//           workgroups per target, a 32 x 32 quadrant each;
+//   then the level's nodes walk their own panels right-looking in lock step, two launches per
+//   panel step over every node of the level that has that panel:
+//   k_ldlt_panel     the diagonal tile's factorisation and the panel row's U / L^T tiles in one
+//           launch (a workgroup per three row tiles, the diagonal wave beside them); the factored
+//           diagonal tile lands in its unused L^T slot;
+//   k_ldlt_ptrail_q  the trailing updates of the nodes' own rows, by quadrants; its copy jobs move
+//           the factored diagonal tile into place.
+// The forward sweep rides along (SpDev::yfused): k_ldlt_yinit sets y = b, and y is one more column
+// of every launch above -- the descendants' terms in the unstored quadrant of k_ldlt_update_q's
+// diagonal targets, y_p as a role of k_ldlt_panel, the panel's terms inside the node as jobs of
+// k_ldlt_ptrail_q.  The backward sweep runs the levels top-down with the ancestors' terms pushed:
+// k_ldlt_binit (y / d), then per level k_ldlt_bin (the level's nodes finish their rows) and
+// k_ldlt_bpush (every row below applies that level's tiles of its row list).  A node of more than
+// kSweepMaxTiles tiles does not fit k_ldlt_bin's LDS: the backward sweep is then one launch per
+// level in which every row walks its ancestor tiles itself (k_ldlt_bwdn_u; k_ldlt_backward, one
+// wave per node, for levels of one-tile or oversized nodes).
+// Nodes of one level share no tile, so their workgroups run concurrently; the descendants' updates
+// of an ancestor tile arrive in ascending K, i.e. in pivot order, as in the sequential sweep.
+//
+// The sharded solve (SparseLdlt::solve_dist) runs the same factor launches restricted by tile class
+// (SpDev::want / kmode), with k_ldlt_update_q writing the separators' deltas into the exchange
+// buffer, but does not fuse the sweeps: after each level's panels the forward sweep is a launch
+// of its own (k_ldlt_fwdn_u, a workgroup per node; k_ldlt_pfwd for one-tile or oversized nodes;
+// k_ldlt_fwd_part for the separator rows' input from this rank's subtrees), and the backward
+// sweep is the per-level k_ldlt_bwdn_u / k_ldlt_backward launches, not the pushed form.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -71,9 +90,7 @@ struct SpDev {
     const int* levNodes;  // node ids by level
     const int4* tgts;     // update targets by level: (slot(I, J), I, J, first K pair)
     const int4* kps;      // (slot(K, I), slot(K, J), K, 0), per target in ascending K
-    const int* stepP;     // panel steps: the panels of (level, step), see k_ldlt_pdiag
-    const int2* rowJobs;  // (panel, index in its row) of each U tile of a step
-    const int2* pairJobs; // (panel, pair index) of each trailing target of a step
+    const int2* pairJobs; // k_ldlt_ptrail_q's jobs of a step: (panel, pair index >= 0 | y term -1 - e | kDiagCopyJob)
     const int4* panelJobs; // (panel, first role, roles, 0): k_ldlt_panel's workgroups of a step
     uint8_t* lnz;
     double* y;            // tile space
@@ -83,10 +100,9 @@ struct SpDev {
     const uint8_t* tcls;  // tile class: 0 another rank's subtree, 1 shared separator, 2 this rank's subtree
     int want;             // launches touch the targets / panels / nodes of this class only (-1: all)
     int kmode;            // 0: every pivot tile K; 1 / 2: only K of that class (updates, forward sweep)
-    double* dst;          // k_ldlt_update delta mode: the target tiles live in the exchange buffer
+    double* dst;          // k_ldlt_update_q delta mode: the target tiles live in the exchange buffer
     const int* packIdx;   // slot -> tile index in dst (delta mode)
     int yfused;           // the forward sweep rides along the factorisation (y as an extra column)
-    int pfused;           // k_ldlt_panel: factored diagonal tiles land in their L^T slot, copied by k_ldlt_ptrail_q
 };
 constexpr int kDiagCopyJob = -2147483647 - 1;   // pairJobs marker: copy the panel's factored diagonal tile
 
@@ -121,500 +137,30 @@ __device__ __forceinline__ double rdlane(double v, int l) {
     return __longlong_as_double(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
 }
 
-// A(I, J) -= L(I, K) U(K, J) over a target's descendant tile rows K (ascending): 256 threads,
-// 4 x 4 register micro-tiles, the two operand tiles staged in LDS per K.
-__global__ void __launch_bounds__(256) k_ldlt_update(SpDev S, int t0) {
-    __shared__ double Lg[LT * LT];   // [k][i] = L[I0 + i][K0 + k]
-    __shared__ double Ug[LT * LT];   // [k][j] = U[K0 + k][J0 + j]
-    if (*(volatile int*)S.fail) return;
-    const int4 tg = S.tgts[t0 + blockIdx.x];
-    const int kp0 = tg.w, kp1 = S.tgts[t0 + blockIdx.x + 1].w;
-    const int I = tg.y, J = tg.z;
-    if (skip_tile(S, I)) return;
-    const int ih = S.th[I], jw = S.th[J];
-    const int gt = threadIdx.x, ty = gt >> 4, tx = gt & 15;
-    double* T = S.dst ? S.dst + (size_t)S.packIdx[tg.x] * (LT * LT) : S.U + (size_t)tg.x * (LT * LT);
-    double acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int bb = 0; bb < 4; bb++) {
-            const int i = ty + 16 * a, j = tx + 16 * bb;
-            acc[a][bb] = (i < ih && j < jw) ? T[i * LT + j] : 0.0;
-        }
-    for (int q = kp0; q < kp1; q++) {
-        const int4 kp = S.kps[q];
-        if (!S.lnz[kp.x] || !S.lnz[kp.y] || skip_k(S, kp.z)) continue;   // block-uniform
-        const double2* srcL = (const double2*)(S.LT + (size_t)kp.x * (LT * LT));
-        const double2* srcU = (const double2*)(S.U + (size_t)kp.y * (LT * LT));
-        __syncthreads();
-#pragma unroll
-        for (int u = 0; u < (LT * LT / 2) / 256; u++) {
-            ((double2*)Lg)[gt + 256 * u] = srcL[gt + 256 * u];
-            ((double2*)Ug)[gt + 256 * u] = srcU[gt + 256 * u];
-        }
-        __syncthreads();
-        const int kw = S.th[kp.z];
-        for (int k = 0; k < kw; k++) {
-            double l[4], u[4];
-#pragma unroll
-            for (int a = 0; a < 4; a++) l[a] = Lg[k * LT + ty + 16 * a];
-#pragma unroll
-            for (int bb = 0; bb < 4; bb++) u[bb] = Ug[k * LT + tx + 16 * bb];
-#pragma unroll
-            for (int a = 0; a < 4; a++)
-#pragma unroll
-                for (int bb = 0; bb < 4; bb++) acc[a][bb] -= l[a] * u[bb];
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int bb = 0; bb < 4; bb++) {
-            const int i = ty + 16 * a, j = tx + 16 * bb;
-            if (i < ih && j < jw && (I != J || i <= j)) T[i * LT + j] = acc[a][bb];
-        }
-}
-
-// A level's nodes factor their own panels right-looking, panel step by panel step: step s
-// takes panel T0 + s of every node of the level that has one, in three launches (diagonal
-// tile, the panel row's U / L^T tiles, the trailing updates inside the nodes), so every tile
-// of a step is its own workgroup.  Then k_ldlt_pfwd solves the level's rows of L y = b.
-
-// Diagonal tile of each panel of the step: one wave per panel, lane = column.  On exit the tile
-// holds U (d on the diagonal) in its upper triangle and L strictly below.
-__global__ void __launch_bounds__(64) k_ldlt_pdiag(SpDev S, int j0) {
-    __shared__ double Ls[LT * LP];
-    if (*(volatile int*)S.fail) return;
-    const int p = S.stepP[j0 + blockIdx.x];
-    if (skip_tile(S, p)) return;
-    const int lane = threadIdx.x;
-    const int pw = S.th[p];
-    const __amdgpu_buffer_rsrc_t Ud = tile_rsrc(S.U + (size_t)S.slotOf[(size_t)p * S.nt + p] * (LT * LT));
-    const int vo = lane * 8;
-    double col[LT];
-#pragma unroll
-    for (int r = 0; r < LT; r++) col[r] = tld(Ud, vo, r * LT * 8);
-    bool bad = false;
-#pragma unroll
-    for (int k = 0; k < LT; k++) {
-        if (k < pw && !bad) {
-            const double d = rdlane(col[k], k);   // the pivot, from lane k's register (no LDS round trip)
-            if (d == 0.0) {
-                bad = true;
-            } else {
-                Ls[k * LP + lane] = lane > k ? col[k] / d : 0.0;
-                __builtin_amdgcn_wave_barrier();
-                const double ck = col[k];
-#pragma unroll
-                for (int i = k + 1; i < LT; i++) col[i] -= Ls[k * LP + i] * ck;
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-    }
-    if (bad) {
-        if (lane == 0) *S.fail = 1;
-        return;
-    }
-#pragma unroll
-    for (int r = 0; r < LT; r++)
-        if (r < pw && lane < pw) tst(Ud, lane >= r ? col[r] : Ls[lane * LP + r], vo, r * LT * 8);
-}
-
-// U tiles (p, J > p) of each panel row of the step: one wave per tile, lane = column; the
-// panel's L and d come from its factored diagonal tile (padding pivots: L = 0, d = 1).
-__global__ void __launch_bounds__(64) k_ldlt_prow(SpDev S, int j0) {
-    __shared__ double Ls[LT * LP];   // [k][i] = L[i][k]
-    __shared__ double dsh[LT];
-    if (*(volatile int*)S.fail) return;
-    const int2 job = S.rowJobs[j0 + blockIdx.x];   // (panel, index in its row)
-    const int p = job.x, lane = threadIdx.x;
-    if (job.y < 0 || skip_tile(S, p)) return;   // (y jobs: the four-wave kernel's only)
-    const int pw = S.th[p];
-    const double* D = S.U + (size_t)S.slotOf[(size_t)p * S.nt + p] * (LT * LT);
-    // L[i][k] = D[i][k] (i > k) into Ls[k][i]: row r of D read by the wave in one coalesced load
-    // (lane = column k) per row, instead of a 512-B-strided column gather per k
-#pragma unroll 4
-    for (int r = 0; r < LT; r++) {
-        const double v = D[r * LT + lane];
-        Ls[lane * LP + r] = (lane < pw && r > lane) ? v : 0.0;
-    }
-    dsh[lane] = lane < pw ? D[lane * LT + lane] : 1.0;
-    __syncthreads();
-    const int e = S.rowStart[p] + job.y;
-    const int sl = S.rowSlot[e];
-    const __amdgpu_buffer_rsrc_t Ut = tile_rsrc(S.U + (size_t)sl * (LT * LT));
-    const __amdgpu_buffer_rsrc_t Lo = tile_rsrc(S.LT + (size_t)sl * (LT * LT));
-    const int vo = lane * 8;
-    double c[LT];
-#pragma unroll
-    for (int r = 0; r < LT; r++) c[r] = tld(Ut, vo, r * LT * 8);   // zero outside the system
-    // per element the updates arrive in k order (the oracle's); the scheduling barrier keeps the
-    // compiler from hoisting every pivot's 63 broadcast reads at once
-#pragma unroll
-    for (int k = 0; k < LT - 1; k++) {
-        const double ck = c[k];
-#pragma unroll
-        for (int i = k + 1; i < LT; i++) c[i] -= Ls[k * LP + i] * ck;   // L[i][k], wave-uniform address
-        __builtin_amdgcn_sched_barrier(0);
-    }
-    bool nz = false;
-#pragma unroll
-    for (int r = 0; r < LT; r++) {
-        tst(Ut, c[r], vo, r * LT * 8);
-        nz |= c[r] != 0.0;
-        tst(Lo, c[r] / dsh[r], vo, r * LT * 8);
-    }
-    // flag = some eliminated U[k][j] != 0, a superset of "some l != 0": skipping on it is exact
-    const bool any = __any(nz);
-    if (lane == 0) S.lnz[sl] = any ? 1 : 0;
-}
-
-// The same two kernels with a rolled pivot loop.  Fully unrolled, k_ldlt_pdiag / k_ldlt_prow are
-// 69 / 59 KB of straight-line code that every launch runs once, so the wave waits on instruction
-// fetch; here a loop over 8-pivot chunks runs one 8-pivot body (~9 KB): register t of the chunk
-// is pivot 8c + t, the live column shifts down by 8 registers after each chunk, and groups of 8
-// registers past the live rows are skipped.  Per element the updates still arrive in ascending
-// pivot order (the same operations as the unrolled kernels and the oracle); padding pivots
-// (k >= pw), whose L is zero, are not applied (the oracle has no such rows).
+// A level's nodes factor their own panels right-looking, panel step by panel step: step s takes
+// panel T0 + s of every node of the level that has one, in two launches (k_ldlt_panel: the
+// diagonal tile and the panel row's U / L^T tiles; k_ldlt_ptrail_q: the trailing updates inside
+// the nodes).
+//
+// k_ldlt_panel: a panel step's diagonal factorisation and its panel row's eliminations in one
+// launch, a workgroup of 1 + R waves per group of up to R roles of a panel (a role: one row tile
+// (p, J > p), or after them the fused forward sweep's y_p with its column in lane 0).  Wave 0 holds
+// the diagonal tile (lane = column) and, per pivot k, publishes d_k and the column of L in LDS;
+// after one barrier every wave applies pivot k to its own tile (wave 1 + r: role r of the group,
+// lane = column), so a row tile's elimination runs in lock step with the diagonal and the diagonal
+// tile is loaded once.  Every group of a panel factors the diagonal redundantly (the same
+// operations); the first one stores it -- into the tile's unused L^T slot, since the other groups
+// of the launch read the unfactored tile from U; the next launch (k_ldlt_ptrail_q's copy jobs)
+// moves it into place.  Per element: pivots ascending, l = u / d, a -= l * u, L^T = u / d_k;
+// padding pivots (k >= pw), whose L is zero, are not applied (the oracle has no such rows).
+// The pivot loop is rolled over 8-pivot chunks (fully unrolled, the 64 pivots are ~60 KB of
+// straight-line code that every launch runs once, so the wave waits on instruction fetch):
+// register t of the chunk is pivot 8c + t, the live column shifts down by 8 registers after each
+// chunk, and groups of 8 registers past the live rows are skipped.
 constexpr int kChunk = 8;
-
-__global__ void __launch_bounds__(64) k_ldlt_pdiag_r(SpDev S, int j0) {
-    __shared__ double Ls[LT * LP];
-    if (*(volatile int*)S.fail) return;
-    const int p = S.stepP[j0 + blockIdx.x];
-    if (skip_tile(S, p)) return;
-    const int lane = threadIdx.x;
-    const int pw = S.th[p];
-    const __amdgpu_buffer_rsrc_t Ud = tile_rsrc(S.U + (size_t)S.slotOf[(size_t)p * S.nt + p] * (LT * LT));
-    const int vo = lane * 8;
-    double col[LT];   // col[r] = tile row kb + r of column `lane` (kb: the chunk's first pivot)
-#pragma unroll
-    for (int r = 0; r < LT; r++) col[r] = tld(Ud, vo, r * LT * 8);
-    bool bad = false;
-    for (int c = 0; c < LT / kChunk; c++) {
-        const int kb = kChunk * c;
-        if (kb >= pw || bad) break;
-#pragma unroll
-        for (int t = 0; t < kChunk; t++) {
-            const int k = kb + t;
-            if (k < pw && !bad) {
-                const double d = rdlane(col[t], k);
-                if (d == 0.0) {
-                    bad = true;
-                } else {
-                    Ls[k * LP + lane] = lane > k ? col[t] / d : 0.0;
-                    __builtin_amdgcn_wave_barrier();
-                    // row k is final: U (lane >= k) and the L of the earlier pivots (lane < k)
-                    if (lane < pw) tst(Ud, lane >= k ? col[t] : Ls[lane * LP + k], vo, k * LT * 8);
-                    const double ck = col[t];
-#pragma unroll
-                    for (int q = 0; q < LT / kChunk; q++) {
-                        if (q < LT / kChunk - c) {   // registers 8q..8q+7 hold live rows
-#pragma unroll
-                            for (int r = kChunk * q; r < kChunk * q + kChunk; r++)
-                                if (r > t) col[r] -= Ls[k * LP + kb + r] * ck;
-                        }
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < LT - kChunk; r++) col[r] = col[r + kChunk];
-    }
-    if (bad && lane == 0) *S.fail = 1;
-}
-
-__global__ void __launch_bounds__(64) k_ldlt_prow_r(SpDev S, int j0) {
-    __shared__ double Ls[LT * LP];   // [k][i] = L[i][k]
-    __shared__ double dsh[LT];
-    if (*(volatile int*)S.fail) return;
-    const int2 job = S.rowJobs[j0 + blockIdx.x];   // (panel, index in its row)
-    const int p = job.x, lane = threadIdx.x;
-    if (job.y < 0 || skip_tile(S, p)) return;   // (y jobs: the four-wave kernel's only)
-    const int pw = S.th[p];
-    const double* D = S.U + (size_t)S.slotOf[(size_t)p * S.nt + p] * (LT * LT);
-    for (int r = 0; r < LT; r++) {
-        const double v = D[r * LT + lane];
-        Ls[lane * LP + r] = (lane < pw && r > lane) ? v : 0.0;
-    }
-    dsh[lane] = lane < pw ? D[lane * LT + lane] : 1.0;
-    __syncthreads();
-    const int e = S.rowStart[p] + job.y;
-    const int sl = S.rowSlot[e];
-    const __amdgpu_buffer_rsrc_t Ut = tile_rsrc(S.U + (size_t)sl * (LT * LT));
-    const __amdgpu_buffer_rsrc_t Lo = tile_rsrc(S.LT + (size_t)sl * (LT * LT));
-    const int vo = lane * 8;
-    double c[LT];   // c[r] = tile row kb + r of column `lane`
-#pragma unroll
-    for (int r = 0; r < LT; r++) c[r] = tld(Ut, vo, r * LT * 8);   // zero outside the system
-    bool nz = false;
-    for (int ch = 0; ch < LT / kChunk; ch++) {
-        const int kb = kChunk * ch;
-        if (kb >= pw) break;
-#pragma unroll
-        for (int t = 0; t < kChunk; t++) {
-            const int k = kb + t;
-            if (k < pw) {
-                const double ck = c[t];   // row k final: all its updates (pivots < k) are in
-                tst(Ut, ck, vo, k * LT * 8);
-                tst(Lo, ck / dsh[k], vo, k * LT * 8);
-                nz |= ck != 0.0;
-#pragma unroll
-                for (int q = 0; q < LT / kChunk; q++) {
-                    if (q < LT / kChunk - ch) {
-#pragma unroll
-                        for (int r = kChunk * q; r < kChunk * q + kChunk; r++)
-                            if (r > t) c[r] -= Ls[k * LP + kb + r] * ck;   // L[kb + r][k], wave-uniform address
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-#pragma unroll
-        for (int r = 0; r < LT - kChunk; r++) c[r] = c[r + kChunk];
-    }
-    for (int r = pw; r < LT; r++) tst(Lo, 0.0, vo, r * LT * 8);   // padding rows of L^T: zero
-    // flag = some eliminated U[k][j] != 0, a superset of "some l != 0": skipping on it is exact
-    const bool any = __any(nz);
-    if (lane == 0) S.lnz[sl] = any ? 1 : 0;
-}
-
-// U tiles of the panel rows with four waves per tile: wave w takes columns 16w..16w+15, a
-// quad of lanes per column, lane s of the quad rows 4q + s (q < 16).  Pivot k's row value
-// reaches the quad by one DPP broadcast from lane k mod 4, every lane applies it to its own
-// rows below k with the L it reads from LDS (four distinct addresses per instruction), so a
-// wave issues a quarter of the one-wave kernel's FP64 work and the four waves run on the
-// CU's four SIMDs without any barrier.  The lane's rows shift down by one register after every
-// four pivots (pivot 4m + t is register 0 of quad lane t).  Same per-element sequence.
-__device__ __forceinline__ double quad_bcast(double v, int t) {
-    const unsigned long long u = __double_as_longlong(v);
-    int lo = (int)(u & 0xffffffffu), hi = (int)(u >> 32);
-    const int ctl = t | (t << 2) | (t << 4) | (t << 6);   // quad_perm(t, t, t, t)
-    switch (t) {   // the DPP control is an immediate
-    case 0:
-        lo = __builtin_amdgcn_mov_dpp(lo, 0x00, 0xf, 0xf, false);
-        hi = __builtin_amdgcn_mov_dpp(hi, 0x00, 0xf, 0xf, false);
-        break;
-    case 1:
-        lo = __builtin_amdgcn_mov_dpp(lo, 0x55, 0xf, 0xf, false);
-        hi = __builtin_amdgcn_mov_dpp(hi, 0x55, 0xf, 0xf, false);
-        break;
-    case 2:
-        lo = __builtin_amdgcn_mov_dpp(lo, 0xaa, 0xf, 0xf, false);
-        hi = __builtin_amdgcn_mov_dpp(hi, 0xaa, 0xf, 0xf, false);
-        break;
-    default:
-        lo = __builtin_amdgcn_mov_dpp(lo, 0xff, 0xf, 0xf, false);
-        hi = __builtin_amdgcn_mov_dpp(hi, 0xff, 0xf, 0xf, false);
-        break;
-    }
-    (void)ctl;
-    return __longlong_as_double(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo);
-}
-
-__global__ void __launch_bounds__(256) k_ldlt_prow4(SpDev S, int j0) {
-    __shared__ double Ls[LT * LP + 4 * LT];   // [k][i] = L[i][k]; the pad keeps dead-row reads in bounds
-    __shared__ double dsh[LT];
-    __shared__ int anyNz;
-    if (*(volatile int*)S.fail) return;
-    const int2 job = S.rowJobs[j0 + blockIdx.x];   // (panel, index in its row; -1: the panel's y)
-    const int p = job.x, tid = threadIdx.x;
-    if (skip_tile(S, p)) return;
-    const bool yj = job.y < 0;   // fused forward sweep: y_p as one more column of the panel row
-    if (yj && !S.yfused) return;
-    const int pw = S.th[p];
-    const double* D = S.U + (size_t)S.slotOf[(size_t)p * S.nt + p] * (LT * LT);
-    {   // L of the panel from its factored diagonal tile: 16 coalesced row loads in flight per thread
-        const int col = tid & 63, r0 = tid >> 6;
-        double v[LT / 4];
-#pragma unroll
-        for (int u = 0; u < LT / 4; u++) v[u] = D[(r0 + 4 * u) * LT + col];
-#pragma unroll
-        for (int u = 0; u < LT / 4; u++) {
-            const int r = r0 + 4 * u;
-            Ls[col * LP + r] = (col < pw && r > col) ? v[u] : 0.0;
-        }
-        if (tid < LT) dsh[tid] = tid < pw ? D[tid * LT + tid] : 1.0;
-        if (tid == 0) anyNz = 0;
-    }
-    __syncthreads();
-    const int e = S.rowStart[p] + (yj ? 0 : job.y);
-    const int sl = S.rowSlot[e];   // (a y job keeps a valid slot: its descriptors are never used to store)
-    const __amdgpu_buffer_rsrc_t Ut = tile_rsrc(S.U + (size_t)sl * (LT * LT));
-    const __amdgpu_buffer_rsrc_t Lo = tile_rsrc(S.LT + (size_t)sl * (LT * LT));
-    const int w = tid >> 6, lane = tid & 63, s = lane & 3, j = 16 * w + (lane >> 2);
-    const int vo = j * 8;
-    double* yp = S.y + p * LT;
-    double c[LT / 4];   // c[q] = tile row 4 (m + q) + s of column j (m: the pivot group)
-    if (yj) {
-#pragma unroll
-        for (int q = 0; q < LT / 4; q++) c[q] = j == 0 ? yp[4 * q + s] : 0.0;
-    } else {
-#pragma unroll
-        for (int q = 0; q < LT / 4; q++) c[q] = tld(Ut, vo, (4 * q + s) * LT * 8);
-    }
-    bool nz = false;
-    for (int m = 0; m < LT / 4; m++) {
-        if (4 * m >= pw) break;
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const int k = 4 * m + t;
-            if (k < pw) {
-                const double ck = quad_bcast(c[0], t);   // row k of column j: final
-                if (s == t) {
-                    if (yj) {
-                        if (j == 0) yp[k] = ck;
-                    } else {
-                        tst(Ut, ck, vo, k * LT * 8);
-                        tst(Lo, ck / dsh[k], vo, k * LT * 8);
-                        nz |= ck != 0.0;
-                    }
-                }
-                const double* Lk = Ls + k * LP + 4 * m + s;   // Lk[4 q] = L[4 (m + q) + s][k]
-                {
-                    const double v = c[0] - Lk[0] * ck;
-                    c[0] = s > t ? v : c[0];
-                }
-#pragma unroll
-                for (int g = 0; g < 4; g++) {
-                    if (4 * g <= LT / 4 - 1 - m) {   // registers 4g..4g+3 hold some live row
-#pragma unroll
-                        for (int q = 4 * g; q < 4 * g + 4; q++)
-                            if (q > 0) c[q] -= Lk[4 * q] * ck;
-                    }
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < LT / 4 - 1; q++) c[q] = c[q + 1];
-        c[LT / 4 - 1] = 0.0;
-    }
-    if (yj) return;   // uniform: the y job stores nothing else
-#pragma unroll
-    for (int q = 0; q < LT / 4; q++) {   // padding rows of L^T: zero
-        const int r = 4 * q + s;
-        if (r >= pw) tst(Lo, 0.0, vo, r * LT * 8);
-    }
-    // flag = some eliminated U[k][j] != 0, a superset of "some l != 0": skipping on it is exact
-    if (__any(nz) && lane == 0) atomicOr(&anyNz, 1);
-    __syncthreads();
-    if (tid == 0) S.lnz[sl] = anyNz ? 1 : 0;
-}
-
-// The diagonal tile with the same four-wave quad layout.  Pivot k: the quad of column k
-// publishes d_k; after a barrier every column's quad forms its l = u_kj / d_k (the column index
-// as a row index), stores row k of the tile (U right of the diagonal, the earlier pivots' L left
-// of it) and publishes l; after a second barrier every lane applies pivot k to its rows below k.
-// Per element the oracle's sequence; lower-triangle registers carry values nobody reads.
-__global__ void __launch_bounds__(256) k_ldlt_pdiag4(SpDev S, int j0) {
-    __shared__ double Ls[LT * LP + 4 * LT];   // [k][i] = L[i][k]; the pad keeps dead-row reads in bounds
-    __shared__ double dk[2];
-    if (*(volatile int*)S.fail) return;
-    const int p = S.stepP[j0 + blockIdx.x];
-    if (skip_tile(S, p)) return;
-    const int tid = threadIdx.x;
-    const int pw = S.th[p];
-    const __amdgpu_buffer_rsrc_t Ud = tile_rsrc(S.U + (size_t)S.slotOf[(size_t)p * S.nt + p] * (LT * LT));
-    const int w = tid >> 6, lane = tid & 63, s = lane & 3, j = 16 * w + (lane >> 2);
-    const int vo = j * 8;
-    double c[LT / 4];   // c[q] = tile row 4 (m + q) + s of column j
-#pragma unroll
-    for (int q = 0; q < LT / 4; q++) c[q] = tld(Ud, vo, (4 * q + s) * LT * 8);
-    bool bad = false;
-    for (int m = 0; m < LT / 4 && !bad; m++) {
-        if (4 * m >= pw) break;
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const int k = 4 * m + t;
-            if (k < pw && !bad) {
-                const double ck = quad_bcast(c[0], t);   // row k of column j: final
-                if (j == k && s == t) dk[k & 1] = ck;
-                __syncthreads();
-                const double d = dk[k & 1];
-                if (d == 0.0) {   // uniform
-                    bad = true;
-                } else {
-                    if (s == t) {
-                        if (j < pw) tst(Ud, j >= k ? ck : Ls[j * LP + k], vo, k * LT * 8);
-                        Ls[k * LP + j] = j > k ? ck / d : 0.0;   // L[j][k]
-                    }
-                    __syncthreads();
-                    const double* Lk = Ls + k * LP + 4 * m + s;   // Lk[4 q] = L[4 (m + q) + s][k]
-                    {
-                        const double v = c[0] - Lk[0] * ck;
-                        c[0] = s > t ? v : c[0];
-                    }
-#pragma unroll
-                    for (int g = 0; g < 4; g++) {
-                        if (4 * g <= LT / 4 - 1 - m) {
-#pragma unroll
-                            for (int q = 4 * g; q < 4 * g + 4; q++)
-                                if (q > 0) c[q] -= Lk[4 * q] * ck;
-                        }
-                    }
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-        }
-#pragma unroll
-        for (int q = 0; q < LT / 4 - 1; q++) c[q] = c[q + 1];
-        c[LT / 4 - 1] = 0.0;
-    }
-    if (bad && tid == 0) *S.fail = 1;
-}
-
-// ORBGPU_LDLT_PROW=1 keeps the one-wave panel-row kernel (A/B)
-static bool prow_quads() {
-    static const bool v = [] {
-        const char* e = getenv("ORBGPU_LDLT_PROW");
-        return !(e && e[0] == '1');
-    }();
-    return v;
-}
-
-// ORBGPU_LDLT_PDIAG4=1 takes the four-wave diagonal kernel
-static bool pdiag_quads() {
-    static const bool v = [] {
-        const char* e = getenv("ORBGPU_LDLT_PDIAG4");
-        return e && e[0] == '1';
-    }();
-    return v;
-}
-
-// ORBGPU_LDLT_ROLL=0 keeps the fully unrolled panel kernels (A/B)
-static bool rolled_panels() {
-    static const bool v = [] {
-        const char* e = getenv("ORBGPU_LDLT_ROLL");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
-
-// A panel step's diagonal factorisation and its panel row's eliminations in ONE launch
-// (k_ldlt_pdiag_r + k_ldlt_prow4 fused): a 512-thread workgroup per group of up to 7 row tiles
-// of a panel.  Wave 0 holds the diagonal tile (lane = column) and, per pivot k, publishes d_k and
-// the column of L in LDS; after one barrier every wave applies pivot k to its own tile (wave
-// 1 + r: row tile r of the group, lane = column; the fused forward sweep's y_p rides as one more
-// role with its column in lane 0), so a row tile's elimination runs in lock step with the
-// diagonal instead of after it, and the diagonal tile is not reloaded.  Every group of a panel
-// factors the diagonal redundantly (the same operations); the first one stores it -- into the
-// tile's unused L^T slot, since the other groups of the launch read the unfactored tile from U;
-// the next launch (k_ldlt_ptrail_q's copy jobs) moves it into place.  Per element
-// the sequence of k_ldlt_pdiag_r / k_ldlt_prow4: pivots ascending, l = u / d, a -= l * u, L^T =
-// u / d_k; padding pivots (k >= pw) not applied.
-// row tiles (or y) per workgroup beside the diagonal wave: R + 1 waves share the CU's FP64 issue,
-// so R = 3 (one wave per SIMD) by default; ORBGPU_LDLT_PANEL_ROLES = 1 / 3 / 7 (A/B)
-static int panel_roles() {
-    static const int v = [] {
-        const char* e = getenv("ORBGPU_LDLT_PANEL_ROLES");
-        const int r = e ? atoi(e) : 3;
-        return (r == 1 || r == 7) ? r : 3;
-    }();
-    return v;
-}
+// roles per workgroup beside the diagonal wave: the 1 + R waves share the CU's FP64 issue, so
+// one wave per SIMD (7 measured slower, 1 the same for three times the workgroups)
+constexpr int kPanelRoles = 3;
 
 template <int R>
 __global__ void __launch_bounds__(64 * (1 + R)) k_ldlt_panel(SpDev S, int j0) {
@@ -708,69 +254,9 @@ __global__ void __launch_bounds__(64 * (1 + R)) k_ldlt_panel(SpDev S, int j0) {
     }
 }
 
-// ORBGPU_LDLT_PANEL=0 keeps the separate diagonal and panel-row launches (A/B)
-static bool fused_panels() {
-    static const bool v = [] {
-        const char* e = getenv("ORBGPU_LDLT_PANEL");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
-
-// Trailing updates inside the nodes: A(I, J) -= L(I, p) U(p, J), one 256-thread workgroup per
-// target of the step (4 x 4 register micro-tiles, both operand tiles staged in LDS).
-__global__ void __launch_bounds__(256) k_ldlt_ptrail(SpDev S, int j0) {
-    __shared__ double Lg[LT * LT];   // [k][i] = L[I0 + i][p0 + k]
-    __shared__ double Ug[LT * LT];   // [k][j] = U[p0 + k][J0 + j]
-    if (*(volatile int*)S.fail) return;
-    const int2 job = S.pairJobs[j0 + blockIdx.x];   // (panel, pair index)
-    const int p = job.x;
-    if (job.y < 0 || skip_tile(S, p)) return;   // (y jobs: the quadrant kernel's only)
-    const int rs = S.rowStart[p];
-    const int4 pr = S.pairs[S.pairStart[p] + job.y];
-    const int slI = S.rowSlot[rs + pr.x], slJ = S.rowSlot[rs + pr.y];
-    if (!S.lnz[slI] || !S.lnz[slJ]) return;   // block-uniform
-    const int gt = threadIdx.x, ty = gt >> 4, tx = gt & 15;
-    const double2* srcL = (const double2*)(S.LT + (size_t)slI * (LT * LT));
-    const double2* srcU = (const double2*)(S.U + (size_t)slJ * (LT * LT));
-#pragma unroll
-    for (int u = 0; u < (LT * LT / 2) / 256; u++) {
-        ((double2*)Lg)[gt + 256 * u] = srcL[gt + 256 * u];
-        ((double2*)Ug)[gt + 256 * u] = srcU[gt + 256 * u];
-    }
-    __syncthreads();
-    const int I = S.rowJ[rs + pr.x], J = S.rowJ[rs + pr.y];
-    const int ih = S.th[I], jw = S.th[J], pw = S.th[p];
-    double* T = S.U + (size_t)pr.z * (LT * LT);
-    double acc[4][4];
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int bb = 0; bb < 4; bb++) {
-            const int i = ty + 16 * a, j = tx + 16 * bb;
-            acc[a][bb] = (i < ih && j < jw) ? T[i * LT + j] : 0.0;
-        }
-    for (int k = 0; k < pw; k++) {
-        double l[4], u[4];
-#pragma unroll
-        for (int a = 0; a < 4; a++) l[a] = Lg[k * LT + ty + 16 * a];
-#pragma unroll
-        for (int bb = 0; bb < 4; bb++) u[bb] = Ug[k * LT + tx + 16 * bb];
-#pragma unroll
-        for (int a = 0; a < 4; a++)
-#pragma unroll
-            for (int bb = 0; bb < 4; bb++) acc[a][bb] -= l[a] * u[bb];
-    }
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int bb = 0; bb < 4; bb++) {
-            const int i = ty + 16 * a, j = tx + 16 * bb;
-            if (i < ih && j < jw && (I != J || i <= j)) T[i * LT + j] = acc[a][bb];
-        }
-}
-
-// Quadrant forms of k_ldlt_update / k_ldlt_ptrail.  A 64 x 64 tile update is 524 k FP64
+// The tile updates: k_ldlt_update_q, A(I, J) -= L(I, K) U(K, J) over a target's descendant tile
+// rows K (ascending), and k_ldlt_ptrail_q, A(I, J) -= L(I, p) U(p, J) inside the nodes.  A
+// 64 x 64 tile update is 524 k FP64
 // operations per pivot tile K: one CU (four SIMDs, 16 FP64 lanes each) needs >= 8 k cycles per K
 // whatever its thread count, and a top-level target gathers tens of descendant K in sequence.
 // Four workgroups per target tile, each owning a 32 x 32 quadrant (qi, qj), put four CUs on it:
@@ -943,7 +429,6 @@ __global__ void __launch_bounds__(256) k_ldlt_ptrail_q(SpDev S, int j0) {
     if (skip_tile(S, p)) return;
     const int rs = S.rowStart[p];
     if (job.y == kDiagCopyJob) {   // k_ldlt_panel's factored diagonal tile: L^T shadow -> U, a quarter each
-        if (!S.pfused) return;
         const size_t sd = (size_t)S.slotOf[(size_t)p * S.nt + p] * (LT * LT);
         const d2v* src = (const d2v*)(S.LT + sd) + qd * (LT * LT / 8);
         d2v* dst = (d2v*)(S.U + sd) + qd * (LT * LT / 8);
@@ -980,15 +465,6 @@ __global__ void __launch_bounds__(256) k_ldlt_ptrail_q(SpDev S, int j0) {
     __syncthreads();
     quad_apply(acc, Lg, Ug, pw, ty, tx);
     quad_store(acc, T, qi, qj, ty, tx, ih, jw, I == J);
-}
-
-// ORBGPU_LDLT_QUAD=0 keeps the one-workgroup-per-tile update and trailing kernels (A/B)
-static bool quad_updates() {
-    static const bool v = [] {
-        const char* e = getenv("ORBGPU_LDLT_QUAD");
-        return !(e && e[0] == '0');
-    }();
-    return v;
 }
 
 // L y = b on the rows of each node of a level (one wave per node; lane = row): the descendants'
@@ -1251,8 +727,8 @@ __device__ double bwd_outside(const SpDev& S, int I, int T1, double acc, int lan
     return acc;
 }
 
-// The node sweeps with the pipelined outside phase and wave-uniform LDS operands (ORBGPU_LDLT_SWEEP=2
-// keeps k_ldlt_fwdn / k_ldlt_bwdn for A/B).  Same per-row sequences.
+// The node sweeps: the pipelined outside phase, then the node's own tiles with wave-uniform LDS
+// operands.
 __global__ void __launch_bounds__(64 * kSweepWaves) k_ldlt_fwdn_u(SpDev S, int n0, const double* __restrict__ b) {
     extern __shared__ double accs[];   // [tile - T0][lane]
     __shared__ int cur[kSweepMaxTiles];
@@ -1364,136 +840,12 @@ __global__ void __launch_bounds__(64 * kSweepWaves) k_ldlt_bwdn_u(SpDev S, int n
     }
 }
 
-__global__ void __launch_bounds__(64 * kSweepWaves) k_ldlt_fwdn(SpDev S, int n0, const double* __restrict__ b) {
-    extern __shared__ double accs[];   // [tile - T0][lane]
-    __shared__ int cur[kSweepMaxTiles];   // the tile's first col-list entry inside the node
-    if (*(volatile int*)S.fail) return;
-    const int node = S.levNodes[n0 + blockIdx.x];
-    const int T0 = S.nodeT[2 * node], T1 = S.nodeT[2 * node + 1];
-    if (T1 > T0 && skip_tile(S, T0)) return;
-    const int W = blockDim.x >> 6, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    for (int I = T0 + w; I < T1; I += W) {
-        const int I0 = I * LT;
-        double acc = lane < S.th[I] ? b[S.rowMap[I0 + lane]] : 0.0;
-        int e = S.colStart[I];
-        for (; e < S.colStart[I + 1]; e++) {
-            const int K = S.colK[e];
-            if (K >= T0) break;   // ascending K: the descendants come first
-            const int sl = S.colSlot[e];
-            if (!S.lnz[sl] || skip_k(S, K)) continue;
-            acc = sweep_chain_fwd(acc, S.LT + (size_t)sl * (LT * LT), lane, S.y[K * LT + lane], S.th[K]);
-        }
-        accs[(I - T0) * LT + lane] = acc;
-        if (lane == 0) cur[I - T0] = e;
-    }
-    __syncthreads();
-    for (int s = 0; s < T1 - T0; s++) {
-        const int K = T0 + s, K0 = K * LT, kh = S.th[K];
-        if (s % W == w) {   // the owner: diagonal tile, y_K final
-            const bool on = lane < kh;
-            double acc = accs[s * LT + lane];
-            const double* Ud = S.U + (size_t)S.slotOf[(size_t)K * S.nt + K] * (LT * LT);
-            double Lr[LT];
-#pragma unroll
-            for (int k = 0; k < LT; k++) Lr[k] = (on && k < lane) ? Ud[lane * LT + k] : 0.0;
-#pragma unroll
-            for (int k = 0; k < LT; k++) {
-                if (k < kh) {
-                    const double v = acc - Lr[k] * rdlane(acc, k);
-                    acc = lane > k ? v : acc;
-                }
-            }
-            acc = on ? acc : 0.0;
-            S.y[K0 + lane] = acc;
-            accs[s * LT + lane] = acc;
-        }
-        __syncthreads();
-        const double yk = accs[s * LT + lane];
-        for (int I = T0 + w; I < T1; I += W) {
-            if (I <= K) continue;
-            const int e = cur[I - T0];
-            if (e >= S.colStart[I + 1] || S.colK[e] != K) continue;   // no block (K, I)
-            if (lane == 0) cur[I - T0] = e + 1;
-            const int sl = S.colSlot[e];
-            if (!S.lnz[sl]) continue;
-            accs[(I - T0) * LT + lane] =
-                sweep_chain_fwd(accs[(I - T0) * LT + lane], S.LT + (size_t)sl * (LT * LT), lane, yk, kh);
-        }
-        __syncthreads();
-    }
-}
-
-__global__ void __launch_bounds__(64 * kSweepWaves) k_ldlt_bwdn(SpDev S, int n0, double* __restrict__ x, double* scal,
-                                                                int first) {
-    extern __shared__ double accs[];
-    __shared__ int cur[kSweepMaxTiles];   // the tile's last row-list entry inside the node
-    const int lane = threadIdx.x & 63;
-    const int failed = *(volatile int*)S.fail;
-    if (first && blockIdx.x == 0 && threadIdx.x == 0) scal[3] = failed ? 0.0 : 1.0;
-    if (failed) return;
-    const int node = S.levNodes[n0 + blockIdx.x];
-    const int T0 = S.nodeT[2 * node], T1 = S.nodeT[2 * node + 1];
-    if (T1 > T0 && skip_tile(S, T0)) return;
-    const int W = blockDim.x >> 6, w = threadIdx.x >> 6;
-    for (int I = T0 + w; I < T1; I += W) {
-        const int I0 = I * LT;
-        const double* Ud = S.U + (size_t)S.slotOf[(size_t)I * S.nt + I] * (LT * LT);
-        double acc = lane < S.th[I] ? S.y[I0 + lane] / Ud[lane * LT + lane] : 0.0;
-        int e = S.rowStart[I + 1] - 1;
-        for (; e >= S.rowStart[I]; e--) {
-            const int J = S.rowJ[e];
-            if (J < T1) break;   // descending J: the ancestors come first
-            const int sl = S.rowSlot[e];
-            if (!S.lnz[sl]) continue;
-            acc = sweep_chain_bwd(acc, S.LT + (size_t)sl * (LT * LT), lane, lane < S.th[J] ? S.xs[J * LT + lane] : 0.0,
-                                  S.th[J]);
-        }
-        accs[(I - T0) * LT + lane] = acc;
-        if (lane == 0) cur[I - T0] = e;
-    }
-    __syncthreads();
-    for (int s = T1 - T0 - 1; s >= 0; s--) {
-        const int K = T0 + s, K0 = K * LT, kh = S.th[K];
-        if (s % W == w) {   // the owner: diagonal tile, x_K final
-            const bool on = lane < kh;
-            double acc = accs[s * LT + lane];
-            const double* Ud = S.U + (size_t)S.slotOf[(size_t)K * S.nt + K] * (LT * LT);
-            double Lr[LT];
-#pragma unroll
-            for (int k = 0; k < LT; k++) Lr[k] = (on && k < kh) ? Ud[k * LT + lane] : 0.0;   // L[K0 + k][K0 + lane]
-#pragma unroll
-            for (int k = LT - 1; k >= 0; k--) {
-                if (k < kh) {
-                    const double v = acc - Lr[k] * rdlane(acc, k);
-                    acc = lane < k ? v : acc;
-                }
-            }
-            acc = on ? acc : 0.0;
-            S.xs[K0 + lane] = acc;
-            if (on) x[S.rowMap[K0 + lane]] = acc;
-            accs[s * LT + lane] = acc;
-        }
-        __syncthreads();
-        const double xk = accs[s * LT + lane];
-        for (int I = T0 + w; I < K; I += W) {
-            const int e = cur[I - T0];
-            if (e < S.rowStart[I] || S.rowJ[e] != K) continue;   // no block (I, K)
-            if (lane == 0) cur[I - T0] = e - 1;
-            const int sl = S.rowSlot[e];
-            if (!S.lnz[sl]) continue;
-            accs[(I - T0) * LT + lane] =
-                sweep_chain_bwd(accs[(I - T0) * LT + lane], S.LT + (size_t)sl * (LT * LT), lane, xk, kh);
-        }
-        __syncthreads();
-    }
-}
-
-// Backward sweep by levels with the ancestors' terms PUSHED (the default): per element the
+// Backward sweep by levels with the ancestors' terms PUSHED (SparseLdlt::solve): per element the
 // sequence of k_ldlt_backward (x_i = y_i / d_i, then L[j][i] x_j for j descending), split as
 //   k_ldlt_binit   acc = y / d for every tile row;
 //   per level H, top-down:
 //     k_ldlt_bin     the level's nodes finish their rows from acc: their own tiles, descending
-//                    (the node sweep of k_ldlt_bwdn without its outside phase);
+//                    (the node sweep of k_ldlt_bwdn_u without its outside phase);
 //     k_ldlt_bpush   every tile row below whose ancestor node at level H holds tiles J of its row
 //                    list applies them now: acc_I -= L(J, I)^T x_J, J descending, k descending.
 // A row's ancestors sit on levels above its own and carry larger tile indices the higher they
@@ -1556,7 +908,7 @@ __global__ void __launch_bounds__(256) k_ldlt_bpush(SpDev S, const int4* __restr
 }
 
 // The level's nodes: their rows start from acc (every ancestor term applied), then the node's own
-// tiles one at a time, descending, as in k_ldlt_bwdn.
+// tiles one at a time, descending, as in k_ldlt_bwdn_u (the pivots' x by readlane).
 __global__ void __launch_bounds__(64 * kSweepWaves) k_ldlt_bin(SpDev S, int n0, const double* __restrict__ acc0,
                                                               double* __restrict__ x, double* scal, int first) {
     extern __shared__ double accs[];
@@ -1611,17 +963,6 @@ __global__ void __launch_bounds__(64 * kSweepWaves) k_ldlt_bin(SpDev S, int n0, 
         __syncthreads();
     }
 }
-
-// ORBGPU_LDLT_SWEEP=1 keeps the one-wave-per-node sweeps, =2 the node sweeps with cross-lane
-// broadcasts (A/B); default: the pipelined node sweeps (k_ldlt_fwdn_u / k_ldlt_bwdn_u)
-static int sweep_mode() {
-    static const int v = [] {
-        const char* e = getenv("ORBGPU_LDLT_SWEEP");
-        return e ? atoi(e) : 0;
-    }();
-    return v;
-}
-static bool sweep_nodes() { return sweep_mode() != 1; }
 
 int ldlt_debug_prof(unsigned long long* out8) {
 #ifdef ORBGPU_PROF
@@ -1795,7 +1136,7 @@ int SparseLdlt::build(int n, int g, const std::vector<int>& adjStart, const std:
                 for (int J : rows[I]) {
                     const int first = (int)kps.size();
                     for (int K : cols[I]) {
-                        if (K >= t0) break;   // the node's own panels: right-looking in k_ldlt_factor
+                        if (K >= t0) break;   // the node's own panels: right-looking in k_ldlt_panel / k_ldlt_ptrail_q
                         const int sj = slot(K, J);
                         if (sj >= 0) kps.push_back(make_int4(slot(K, I), sj, K, 0));
                     }
@@ -1811,10 +1152,9 @@ int SparseLdlt::build(int n, int g, const std::vector<int>& adjStart, const std:
         for (int q = hLevNodeStart_[h]; q < hLevNodeStart_[h + 1]; q++)
             hLevMaxT_[h] = std::max(hLevMaxT_[h], nodeT[2 * levNodes[q] + 1] - nodeT[2 * levNodes[q]]);
     // panel steps of each level: step s = panel T0 + s of every node of the level that has one;
-    // per step the panels, the U tiles of their rows and the trailing targets inside the nodes
-    std::vector<int> stepP;
-    std::vector<int2> rowJobs, pairJobs;
-    std::vector<int4> panelJobs;   // k_ldlt_panel: per panel, groups of panel_roles() roles (row tiles, then y)
+    // per step k_ldlt_panel's workgroups and the trailing targets inside the nodes
+    std::vector<int2> pairJobs;
+    std::vector<int4> panelJobs;   // per panel, groups of kPanelRoles roles (row tiles, then y)
     hSteps_.clear();
     hLevStepStart_.assign(nLev_ + 1, 0);
     for (int h = 0; h < nLev_; h++) {
@@ -1823,21 +1163,19 @@ int SparseLdlt::build(int n, int g, const std::vector<int>& adjStart, const std:
         for (int q = hLevNodeStart_[h]; q < hLevNodeStart_[h + 1]; q++)
             maxT = std::max(maxT, nodeT[2 * levNodes[q] + 1] - nodeT[2 * levNodes[q]]);
         for (int st = 0; st < maxT; st++) {
-            const int4 rec = make_int4((int)stepP.size(), (int)rowJobs.size(), (int)pairJobs.size(), (int)panelJobs.size());
+            const int2 rec = make_int2((int)pairJobs.size(), (int)panelJobs.size());
             for (int q = hLevNodeStart_[h]; q < hLevNodeStart_[h + 1]; q++) {
                 const int k = levNodes[q];
                 const int pnl = nodeT[2 * k] + st;
                 if (pnl >= nodeT[2 * k + 1]) continue;
-                stepP.push_back(pnl);
-                for (int e = 0; e < rowStart[pnl + 1] - rowStart[pnl]; e++) rowJobs.push_back(make_int2(pnl, e));
-                rowJobs.push_back(make_int2(pnl, -1));   // the fused forward sweep's y_p (skipped unless yfused)
-                const int roles = rowStart[pnl + 1] - rowStart[pnl] + 1, pr = panel_roles();   // row tiles + y_p
-                for (int r0 = 0; r0 < roles; r0 += pr) panelJobs.push_back(make_int4(pnl, r0, std::min(pr, roles - r0), 0));
+                const int roles = rowStart[pnl + 1] - rowStart[pnl] + 1;   // row tiles + y_p
+                for (int r0 = 0; r0 < roles; r0 += kPanelRoles)
+                    panelJobs.push_back(make_int4(pnl, r0, std::min(kPanelRoles, roles - r0), 0));
                 for (int e = 0; e < pairStart[pnl + 1] - pairStart[pnl]; e++) pairJobs.push_back(make_int2(pnl, e));
                 // ... and its y_I -= L(I, p) y_p for the panel row's entries inside the node
                 for (int e = 0; e < rowStart[pnl + 1] - rowStart[pnl]; e++)
                     if (rowJ[rowStart[pnl] + e] < nodeT[2 * k + 1]) pairJobs.push_back(make_int2(pnl, -1 - e));
-                pairJobs.push_back(make_int2(pnl, kDiagCopyJob));   // (k_ldlt_panel runs only)
+                pairJobs.push_back(make_int2(pnl, kDiagCopyJob));
             }
             hSteps_.push_back(rec);
         }
@@ -1865,7 +1203,7 @@ int SparseLdlt::build(int n, int g, const std::vector<int>& adjStart, const std:
         pushT.insert(pushT.end(), pushByLev[h].begin(), pushByLev[h].end());
     }
     hLevPushStart_[nLev_] = (int)pushT.size();
-    hSteps_.push_back(make_int4((int)stepP.size(), (int)rowJobs.size(), (int)pairJobs.size(), (int)panelJobs.size()));   // sentinel
+    hSteps_.push_back(make_int2((int)pairJobs.size(), (int)panelJobs.size()));   // sentinel
     tgts.push_back(make_int4(0, 0, 0, (int)kps.size()));   // sentinel: the last target's K range end
     // every tile a kernel addresses exists (host check before any launch)
     for (int I = 0; I < nt; I++)
@@ -1930,7 +1268,6 @@ int SparseLdlt::build(int n, int g, const std::vector<int>& adjStart, const std:
     offPairs_ = put4(pairs);
     offTgts_ = put4(tgts);
     offKps_ = put4(kps);
-    offStepP_ = put(stepP);
     auto put2 = [&](const std::vector<int2>& v) {
         while (L.size() % 2) L.push_back(0);
         const size_t o = L.size();
@@ -1940,7 +1277,6 @@ int SparseLdlt::build(int n, int g, const std::vector<int>& adjStart, const std:
         }
         return o;
     };
-    offRowJobs_ = put2(rowJobs);
     offPairJobs_ = put2(pairJobs);
     offPanelJobs_ = put4(panelJobs);
     offPush_ = put4(pushT);
@@ -1997,8 +1333,6 @@ SpDev SparseLdlt::dev() const {
     d.levNodes = lists_ + offLevNodes_;
     d.tgts = (const int4*)(lists_ + offTgts_);
     d.kps = (const int4*)(lists_ + offKps_);
-    d.stepP = lists_ + offStepP_;
-    d.rowJobs = (const int2*)(lists_ + offRowJobs_);
     d.pairJobs = (const int2*)(lists_ + offPairJobs_);
     d.panelJobs = (const int4*)(lists_ + offPanelJobs_);
     d.lnz = lnz_;
@@ -2011,62 +1345,24 @@ SpDev SparseLdlt::dev() const {
     d.dst = nullptr;
     d.packIdx = nullptr;
     d.yfused = 0;
-    // the fused panel launch needs the quadrant trailing kernel (its copy jobs) and the y-aware rows
-    d.pfused = (fused_panels() && quad_updates() && prow_quads()) ? 1 : 0;
     return d;
 }
 
 void SparseLdlt::enqueue_factor_level(const SpDev& d, int h, const double* b, hipStream_t s) {
     const int nt = hLevTgtStart_[h + 1] - hLevTgtStart_[h];
-    if (nt > 0) {
-        if (quad_updates())
-            hipLaunchKernelGGL(k_ldlt_update_q, dim3(4 * nt), dim3(256), 0, s, d, hLevTgtStart_[h]);
-        else
-            hipLaunchKernelGGL(k_ldlt_update, dim3(nt), dim3(256), 0, s, d, hLevTgtStart_[h]);
-    }
+    if (nt > 0) hipLaunchKernelGGL(k_ldlt_update_q, dim3(4 * nt), dim3(256), 0, s, d, hLevTgtStart_[h]);
+    // (a step has a panel, so both of its job lists are non-empty: the diagonal copy job at least)
     for (int st = hLevStepStart_[h]; st < hLevStepStart_[h + 1]; st++) {
-        const int4 a = hSteps_[st], z = hSteps_[st + 1];
-        if (d.pfused) {   // diagonal + panel row in one launch
-            if (z.w > a.w) {
-                const int pr = panel_roles();
-                if (pr == 1)
-                    hipLaunchKernelGGL(k_ldlt_panel<1>, dim3(z.w - a.w), dim3(128), 0, s, d, a.w);
-                else if (pr == 7)
-                    hipLaunchKernelGGL(k_ldlt_panel<7>, dim3(z.w - a.w), dim3(512), 0, s, d, a.w);
-                else
-                    hipLaunchKernelGGL(k_ldlt_panel<3>, dim3(z.w - a.w), dim3(256), 0, s, d, a.w);
-            }
-        } else {
-        if (z.x > a.x) {
-            // the four-wave diagonal kernel measured no faster than the rolled one-wave kernel
-            // (38 vs 36-38 us per launch, profiles/r04l3_gba_ldlt_levels.txt): opt-in
-            if (pdiag_quads())
-                hipLaunchKernelGGL(k_ldlt_pdiag4, dim3(z.x - a.x), dim3(256), 0, s, d, a.x);
-            else
-                hipLaunchKernelGGL(rolled_panels() ? k_ldlt_pdiag_r : k_ldlt_pdiag, dim3(z.x - a.x), dim3(64), 0, s, d,
-                                   a.x);
-        }
-        if (z.y > a.y) {
-            if (prow_quads())
-                hipLaunchKernelGGL(k_ldlt_prow4, dim3(z.y - a.y), dim3(256), 0, s, d, a.y);
-            else
-                hipLaunchKernelGGL(rolled_panels() ? k_ldlt_prow_r : k_ldlt_prow, dim3(z.y - a.y), dim3(64), 0, s, d,
-                                   a.y);
-        }
-        }
-        if (z.z > a.z) {
-            if (quad_updates())
-                hipLaunchKernelGGL(k_ldlt_ptrail_q, dim3(4 * (z.z - a.z)), dim3(256), 0, s, d, a.z);
-            else
-                hipLaunchKernelGGL(k_ldlt_ptrail, dim3(z.z - a.z), dim3(256), 0, s, d, a.z);
-        }
+        const int2 a = hSteps_[st], z = hSteps_[st + 1];
+        hipLaunchKernelGGL(k_ldlt_panel<kPanelRoles>, dim3(z.y - a.y), dim3(64 * (1 + kPanelRoles)), 0, s, d, a.y);
+        hipLaunchKernelGGL(k_ldlt_ptrail_q, dim3(4 * (z.x - a.x)), dim3(256), 0, s, d, a.x);
     }
     if (d.yfused) return;   // the forward sweep rode along
     const int nn = hLevNodeStart_[h + 1] - hLevNodeStart_[h];
     const int mt = hLevMaxT_[h];
-    if (sweep_nodes() && mt > 1 && mt <= kSweepMaxTiles)
-        hipLaunchKernelGGL(sweep_mode() == 2 ? k_ldlt_fwdn : k_ldlt_fwdn_u, dim3(nn), dim3(64 * std::min(mt, kSweepWaves)),
-                           sizeof(double) * LT * mt, s, d, hLevNodeStart_[h], b);
+    if (mt > 1 && mt <= kSweepMaxTiles)
+        hipLaunchKernelGGL(k_ldlt_fwdn_u, dim3(nn), dim3(64 * std::min(mt, kSweepWaves)), sizeof(double) * LT * mt, s, d,
+                           hLevNodeStart_[h], b);
     else
         hipLaunchKernelGGL(k_ldlt_pfwd, dim3(nn), dim3(64), 0, s, d, hLevNodeStart_[h], b);
 }
@@ -2074,42 +1370,23 @@ void SparseLdlt::enqueue_factor_level(const SpDev& d, int h, const double* b, hi
 void SparseLdlt::enqueue_backward_level(const SpDev& d, int h, double* x, double* scal, int first, hipStream_t s) {
     const int nn = hLevNodeStart_[h + 1] - hLevNodeStart_[h];
     const int mt = hLevMaxT_[h];
-    if (sweep_nodes() && mt > 1 && mt <= kSweepMaxTiles)
-        hipLaunchKernelGGL(sweep_mode() == 2 ? k_ldlt_bwdn : k_ldlt_bwdn_u, dim3(nn), dim3(64 * std::min(mt, kSweepWaves)),
-                           sizeof(double) * LT * mt, s, d, hLevNodeStart_[h], x, scal, first);
+    if (mt > 1 && mt <= kSweepMaxTiles)
+        hipLaunchKernelGGL(k_ldlt_bwdn_u, dim3(nn), dim3(64 * std::min(mt, kSweepWaves)), sizeof(double) * LT * mt, s, d,
+                           hLevNodeStart_[h], x, scal, first);
     else
         hipLaunchKernelGGL(k_ldlt_backward, dim3(nn), dim3(64), 0, s, d, hLevNodeStart_[h], x, scal, first);
-}
-
-// ORBGPU_LDLT_BPUSH=0 keeps the per-level backward launches that walk every ancestor tile (A/B)
-static bool pushed_backward() {
-    static const bool v = [] {
-        const char* e = getenv("ORBGPU_LDLT_BPUSH");
-        return !(e && e[0] == '0');
-    }();
-    return v;
-}
-
-// ORBGPU_LDLT_FWD=0 keeps the forward sweep as its own per-level launches (A/B)
-static bool fused_forward() {
-    static const bool v = [] {
-        const char* e = getenv("ORBGPU_LDLT_FWD");
-        return !(e && e[0] == '0');
-    }();
-    return v;
 }
 
 int SparseLdlt::solve(const double* b, double* x, double* scal, hipStream_t s) {
     if (n_ <= 0) return 0;
     SpDev d = dev();
-    // the fused forward sweep needs the y-aware kernels (quadrant updates, four-wave panel rows)
-    d.yfused = (fused_forward() && quad_updates() && prow_quads()) ? 1 : 0;
+    d.yfused = 1;
     ORB_HIP_CHECK(hipMemsetAsync(fail_, 0, sizeof(int), s));
-    if (d.yfused) hipLaunchKernelGGL(k_ldlt_yinit, dim3(nt_), dim3(64), 0, s, d, b);
+    hipLaunchKernelGGL(k_ldlt_yinit, dim3(nt_), dim3(64), 0, s, d, b);
     for (int h = 0; h < nLev_; h++) enqueue_factor_level(d, h, b, s);
     int maxT = 0;
     for (int h = 0; h < nLev_; h++) maxT = std::max(maxT, hLevMaxT_[h]);
-    if (pushed_backward() && maxT <= kSweepMaxTiles) {
+    if (maxT <= kSweepMaxTiles) {   // the pushed backward sweep
         const int4* pt = (const int4*)(lists_ + offPush_);
         hipLaunchKernelGGL(k_ldlt_binit, dim3(nt_), dim3(64), 0, s, d, acc_);
         for (int h = nLev_ - 1; h >= 0; h--) {
@@ -2119,7 +1396,7 @@ int SparseLdlt::solve(const double* b, double* x, double* scal, hipStream_t s) {
             const int np = hLevPushStart_[h + 1] - hLevPushStart_[h];
             if (np > 0) hipLaunchKernelGGL(k_ldlt_bpush, dim3(np), dim3(256), 0, s, d, pt + hLevPushStart_[h], acc_);
         }
-    } else {
+    } else {   // a node's accumulators do not fit the LDS: every row walks its ancestor tiles itself
         for (int h = nLev_ - 1; h >= 0; h--) enqueue_backward_level(d, h, x, scal, h == nLev_ - 1 ? 1 : 0, s);
     }
     ORB_HIP_CHECK(hipGetLastError());
@@ -2276,12 +1553,8 @@ int SparseLdlt::solve_dist(double* b, double* x, double* scal, hipStream_t s, Co
     db.packIdx = dPackIdx_;
     for (int h = 0; h < nLev_; h++) {
         const int nt = hLevTgtStart_[h + 1] - hLevTgtStart_[h];
-        if (levSh_[h] && nt > 0) {
-            if (quad_updates())
-                hipLaunchKernelGGL(k_ldlt_update_q, dim3(4 * nt), dim3(256), 0, s, db, hLevTgtStart_[h]);
-            else
-                hipLaunchKernelGGL(k_ldlt_update, dim3(nt), dim3(256), 0, s, db, hLevTgtStart_[h]);
-        }
+        if (levSh_[h] && nt > 0)
+            hipLaunchKernelGGL(k_ldlt_update_q, dim3(4 * nt), dim3(256), 0, s, db, hLevTgtStart_[h]);
     }
     if (nShT_) hipLaunchKernelGGL(k_ldlt_fwd_part, dim3(nShT_), dim3(64), 0, s, d, b, dShT_, xb + nxb);
     ORB_HIP_CHECK(hipGetLastError());

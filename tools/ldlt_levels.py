@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
-"""Launches of the last sparse LDL^T solve in a rocprofv3 kernel trace (k_ldlt_update, the panel
-steps k_ldlt_pdiag / prow / ptrail, k_ldlt_pfwd, k_ldlt_backward; in launch order) with their
-durations and grid sizes.
+"""Launches of the last sparse LDL^T solve in a rocprofv3 kernel trace (k_ldlt_yinit,
+k_ldlt_update_q, the panel steps k_ldlt_panel / k_ldlt_ptrail_q, then k_ldlt_binit and per level
+k_ldlt_bin / k_ldlt_bpush; a sharded solve: k_ldlt_fwdn_u / k_ldlt_pfwd and k_ldlt_bwdn_u /
+k_ldlt_backward instead; in launch order) with their durations and grid sizes.
 usage: ldlt_levels.py kernel_trace.csv"""
 import csv
 import sys

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-6 global-BA pass: the sparse-LDL^T / global-BA GPU tests, the config-5 timing, and a
 # rocprofv3 trace of one BundleAdjustment(10) (kernel stats + the last solve's launches by level).
-# usage: bash tools/r06_gba.sh <tag> [notests]     (env passes through, e.g. ORBGPU_LDLT_QUAD=0)
+# usage: bash tools/r06_gba.sh <tag> [notests]     (env passes through)
 set -o pipefail
 TAG=${1:-r06gba}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
