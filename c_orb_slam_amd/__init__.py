@@ -11,4 +11,5 @@ from .optimizer import (BundleAdjustment, LocalBundleAdjustment, OptimizeEssenti
 
 __all__ = ["ORBextractor", "ORBmatcher", "Frame", "MapPoints", "KP_DTYPE", "OrbGpuError",
            "device_available", "lib"]
+from .ransac import Initializer, PnPsolver, Rng, Sim3Solver  # noqa: F401
 from .vocabulary import BowVector, ORBVocabulary  # noqa: F401

@@ -263,6 +263,11 @@ def lib():
     L.orbgpu_debug_prof_match.argtypes = [vp]
     L.orbgpu_debug_prof_extract.argtypes = [vp]
     L.orbgpu_debug_extract_plan.argtypes = [vp, vp, vp, vp]
+    L.Initializer_create.argtypes = [vp, i32, vp, f32, i32, P(vp)]
+    L.Initializer_destroy.argtypes = [vp]
+    L.Initializer_Initialize.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, P(i32), vp]
+    L.Initializer_enable_timing.argtypes = [vp, i32]
+    L.Initializer_last_timings.argtypes = [vp, vp]
     L.Sim3Solver_create.argtypes = [i32, vp, vp, vp, vp, vp, i32, vp, vp, i32, P(vp)]
     L.Sim3Solver_destroy.argtypes = [vp]
     L.Sim3Solver_set_ransac.argtypes = [vp, C.c_double, i32, i32]
@@ -278,6 +283,13 @@ def lib():
 
 class orb_rng(C.Structure):
     _fields_ = [("tbl", C.c_int32 * 31), ("f", C.c_int32), ("r", C.c_int32)]
+
+
+class orb_init_info(C.Structure):
+    _fields_ = [("SH", C.c_float), ("SF", C.c_float), ("use_H", C.c_int), ("best_it_H", C.c_int),
+                ("best_it_F", C.c_int), ("H21", C.c_float * 9), ("F21", C.c_float * 9), ("n_hyp", C.c_int),
+                ("nGood", C.c_int * 8), ("parallax", C.c_float * 8), ("chosen", C.c_int),
+                ("inliersH", C.c_void_p), ("inliersF", C.c_void_p)]
 
 
 def ptr(a):

@@ -1,4 +1,4 @@
-"""Host mirror of ORB_SLAM2::PnPsolver, ORB_SLAM2::Sim3Solver and
+"""Host mirror of ORB_SLAM2::PnPsolver, ORB_SLAM2::Sim3Solver, ORB_SLAM2::Initializer and
 DUtils::Random over the C ABI.
 
 PnPsolver(...) takes the packed correspondences the reference constructor
@@ -10,7 +10,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import check, lib, orb_rng, ptr
+from ._lib import check, lib, orb_init_info, orb_rng, ptr
 
 
 class Rng:
@@ -65,6 +65,66 @@ class PnPsolver:
         a, b, c = C.c_int(), C.c_int(), C.c_int()
         check(self._L.PnPsolver_get_state(self._h, C.byref(a), C.byref(b), C.byref(c)))
         return a.value, b.value, c.value
+
+
+class Initializer:
+    """ORB_SLAM2::Initializer (include/Initializer.h): the monocular bootstrap on the GPU.
+    K: 3 x 3; keys1: n1 x 2 undistorted keypoint positions of the reference frame."""
+
+    def __init__(self, K, keys1, sigma=1.0, iterations=200):
+        self._L = lib()
+        self.K = np.ascontiguousarray(K, np.float32).reshape(3, 3)
+        self.keys1 = np.ascontiguousarray(keys1, np.float32).reshape(-1, 2)
+        self.iterations = int(iterations)
+        h = C.c_void_p()
+        check(self._L.Initializer_create(ptr(self.K), len(self.keys1), ptr(self.keys1), sigma, self.iterations,
+                                         C.byref(h)), "Initializer_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.Initializer_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def Initialize(self, keys2, matches12, rng: Rng, want_info=True):
+        """-> (ok, R21 3x3, t21 3, vP3D n1x3, vbTriangulated n1, info); the four results are None
+        where the reference returns false.  info: dict of orb_init_info with the two inlier
+        masks over the matches (matches12 >= 0, in order), or None."""
+        keys2 = np.ascontiguousarray(keys2, np.float32).reshape(-1, 2)
+        m12 = np.ascontiguousarray(matches12, np.int32)
+        if len(m12) != len(self.keys1):
+            raise ValueError("matches12 must have one entry per reference key")
+        n1, N = len(self.keys1), int(np.count_nonzero(m12 >= 0))
+        R, t = np.zeros((3, 3), np.float32), np.zeros(3, np.float32)
+        P3D, tri = np.zeros((max(n1, 1), 3), np.float32), np.zeros(max(n1, 1), np.uint8)
+        ok = C.c_int()
+        info = mH = mF = None
+        if want_info:
+            mH, mF = np.zeros(max(N, 1), np.uint8), np.zeros(max(N, 1), np.uint8)
+            info = orb_init_info()
+            info.inliersH, info.inliersF = mH.ctypes.data, mF.ctypes.data
+        check(self._L.Initializer_Initialize(self._h, len(keys2), ptr(keys2), ptr(m12), C.byref(rng.s), ptr(R), ptr(t),
+                                             ptr(P3D), ptr(tri), C.byref(ok), C.byref(info) if want_info else None),
+              "Initializer_Initialize")
+        d = None
+        if want_info:
+            d = dict(SH=info.SH, SF=info.SF, use_H=info.use_H, best_it_H=info.best_it_H, best_it_F=info.best_it_F,
+                     H21=np.array(info.H21, np.float32), F21=np.array(info.F21, np.float32), n_hyp=info.n_hyp,
+                     nGood=list(info.nGood), parallax=list(info.parallax), chosen=info.chosen,
+                     inliersH=mH[:N].astype(bool), inliersF=mF[:N].astype(bool))
+        if not ok.value:
+            return False, None, None, None, None, d
+        return True, R, t, P3D[:n1], tri[:n1].astype(bool), d
+
+    def last_timings(self):
+        ms = np.zeros(4, np.float32)
+        check(self._L.Initializer_last_timings(self._h, ptr(ms)), "Initializer_last_timings")
+        return ms
+
+    def enable_timing(self, on=True):
+        check(self._L.Initializer_enable_timing(self._h, int(on)))
 
 
 def iterate_batch(solvers, nIterations, rngs):

@@ -688,6 +688,54 @@ int PnPsolver_enable_timing(int on);
 int PnPsolver_last_timings(float* ms2, long long* counts2);
 
 /* ======================================================================
+ * Initializer  (reference include/Initializer.h, src/Initializer.cc): the monocular
+ * bootstrap between ORBmatcher_SearchForInitialization and CreateInitialMapMonocular.
+ * Host pointers only.  The handle owns its stream and device buffers; every call makes
+ * one packed upload, four kernel launches and one download and returns with the
+ * results on the host.  Two handles may be used from two threads at once.
+ * ====================================================================== */
+typedef struct Initializer_t* Initializer_h;
+
+/* Initializer(const Frame& ReferenceFrame, float sigma = 1.0, int iterations = 200)
+ * K: 3 x 3 row-major; keys1: n1 x 2, mvKeysUn[i].pt of the reference frame.
+ * ORB_E_INVALID: a null pointer, n1 < 0, iterations < 1, sigma <= 0, a non-finite key or K. */
+int Initializer_create(const float* K, int n1, const float* keys1, float sigma, int iterations,
+                       Initializer_h* out);
+int Initializer_destroy(Initializer_h h);
+
+typedef struct orb_init_info {     /* optional diagnostics, all outputs */
+    float SH, SF; int use_H;       /* RH = SH/(SH+SF) > 0.40f */
+    int best_it_H, best_it_F;      /* iteration whose score won (strict >, earliest wins); -1: none */
+    float H21[9], F21[9];
+    int n_hyp; int nGood[8]; float parallax[8]; int chosen;   /* 8 (H) or 4 (F) motion hypotheses
+                                      (0: the d1/d2 gate failed or no model); chosen = -1 on failure */
+    uint8_t* inliersH; uint8_t* inliersF;   /* optional, N matches each (match order), may be NULL */
+} orb_init_info;
+
+/* bool Initializer::Initialize(const Frame& CurrentFrame, const vector<int>& vMatches12,
+ *                              cv::Mat& R21, cv::Mat& t21, vector<cv::Point3f>& vP3D,
+ *                              vector<bool>& vbTriangulated)
+ * keys2: n2 x 2; matches12: n1 entries, index into keys2 or -1.  The matches are the pairs
+ * (i, matches12[i]) with matches12[i] >= 0 in i order.  rng is advanced by exactly
+ * 8 * iterations draws (the caller owns the reference's SeedRandOnce(0): orb_rng_seed(&g, 0)).
+ * *ok = the reference's return value.  On *ok == 0 R21, t21, vP3D and vbTriangulated are left
+ * untouched; on *ok == 1 vP3D (n1 x 3) and vbTriangulated (n1) hold the chosen hypothesis,
+ * zero / false where CheckRT wrote nothing.  info (may be NULL) is always filled.
+ * ORB_E_INVALID: a null pointer other than info and its two masks, n2 < 0, a non-finite key, a
+ * match index outside [0, n2), or fewer than 8 matches -- the reference would index its
+ * 8-point sets out of range there -- or an rng that was never seeded.  ORB_E_CAPACITY from
+ * 2^22 reference keys on.  Argument errors are reported before the device is touched and the
+ * handle is looked at last (the match checks need its n1): a well-formed call without one
+ * answers ORB_E_NODEVICE where no device is visible (ORB_E_INVALID otherwise). */
+int Initializer_Initialize(Initializer_h h, int n2, const float* keys2, const int32_t* matches12,
+                           orb_rng* rng, float* R21, float* t21, float* vP3D,
+                           uint8_t* vbTriangulated, int* ok, orb_init_info* info);
+/* Measurement (no reference counterpart): HIP-event times of the handle's next calls.
+ * last_timings: ms4 = {hypotheses, select, CheckRT, finish} of the last timed call. */
+int Initializer_enable_timing(Initializer_h h, int on);
+int Initializer_last_timings(Initializer_h h, float* ms4);
+
+/* ======================================================================
  * Sim3Solver  (reference include/Sim3Solver.h:39-137, src/Sim3Solver.cc)
  * ====================================================================== */
 typedef struct Sim3Solver_t* Sim3Solver_h;
