@@ -13,3 +13,4 @@ __all__ = ["ORBextractor", "ORBmatcher", "Frame", "MapPoints", "KP_DTYPE", "OrbG
            "device_available", "lib"]
 from .ransac import Initializer, PnPsolver, Rng, Sim3Solver  # noqa: F401
 from .vocabulary import BowVector, ORBVocabulary  # noqa: F401
+from .keyframe_database import KeyFrameDatabase  # noqa: F401

@@ -263,6 +263,20 @@ def lib():
     L.orbgpu_debug_prof_match.argtypes = [vp]
     L.orbgpu_debug_prof_extract.argtypes = [vp]
     L.orbgpu_debug_extract_plan.argtypes = [vp, vp, vp, vp]
+    L.KeyFrameDatabase_create.argtypes = [vp, P(vp)]
+    L.KeyFrameDatabase_destroy.argtypes = [vp]
+    L.KeyFrameDatabase_add.argtypes = [vp, C.c_int32, vp, vp, i32]
+    L.KeyFrameDatabase_add_batch.argtypes = [vp, i32, vp, vp, vp, vp]
+    L.KeyFrameDatabase_erase.argtypes = [vp, C.c_int32]
+    L.KeyFrameDatabase_clear.argtypes = [vp]
+    L.KeyFrameDatabase_size.argtypes = [vp, P(i32), P(C.c_longlong)]
+    L.KeyFrameDatabase_set_covisibles.argtypes = [vp, C.c_int32, i32, vp]
+    L.KeyFrameDatabase_DetectLoopCandidates.argtypes = [vp, vp, vp]
+    L.KeyFrameDatabase_DetectRelocalizationCandidates.argtypes = [vp, vp, vp]
+    L.KeyFrameDatabase_DetectRelocalizationCandidates_batch.argtypes = [vp, i32, vp, vp]
+    L.KeyFrameDatabase_enable_timing.argtypes = [vp, i32]
+    L.KeyFrameDatabase_last_timings.argtypes = [vp, vp]
+    L.orbgpu_unit_set_kfdb_initial_capacity.argtypes = [i32, i32]
     L.Initializer_create.argtypes = [vp, i32, vp, f32, i32, P(vp)]
     L.Initializer_destroy.argtypes = [vp]
     L.Initializer_Initialize.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, P(i32), vp]
@@ -321,6 +335,18 @@ class orb_undistort(C.Structure):
 class orb_bow(C.Structure):
     _fields_ = [("cap", C.c_int), ("word", C.c_void_p), ("value", C.c_void_p), ("n_words", C.c_int),
                 ("fv_node", C.c_void_p), ("fv_start", C.c_void_p), ("fv_feat", C.c_void_p), ("n_nodes", C.c_int)]
+
+
+class orb_kfdb_query(C.Structure):
+    _fields_ = [("nq", C.c_int), ("word", C.c_void_p), ("value", C.c_void_p), ("n_exclude", C.c_int),
+                ("exclude", C.c_void_p), ("minScore", C.c_float)]
+
+
+class orb_kfdb_result(C.Structure):
+    _fields_ = [("cap", C.c_int), ("cand", C.c_void_p), ("n_cand", C.c_int), ("cap_scored", C.c_int),
+                ("scored_id", C.c_void_p), ("scored_words", C.c_void_p), ("scored_score", C.c_void_p),
+                ("scored_acc", C.c_void_p), ("n_scored", C.c_int), ("n_sharing", C.c_int),
+                ("maxCommonWords", C.c_int), ("minCommonWords", C.c_int), ("bestAccScore", C.c_float)]
 
 
 class pose_frame(C.Structure):

@@ -431,6 +431,83 @@ int ORBvocabulary_transform_features(ORBvocabulary_h h, const uint8_t* desc, int
 int ORBvocabulary_score(ORBvocabulary_h h, const uint32_t* qw, const double* qv, int nq, int count,
                         const int32_t* cstart, const uint32_t* cw, const double* cv, double* scores);
 
+/* ======================================================================
+ * KeyFrameDatabase (reference include/KeyFrameDatabase.h, src/KeyFrameDatabase.cc)
+ * A device-resident database: every stored keyframe's BowVector lives in device memory and a
+ * query scans all of them.  A word's inverted-file list is the live keyframes holding the word in
+ * the order of their add calls, so lKFsSharingWords is, in closed form, the sharing keyframes in
+ * ascending (index in the query BowVector of the first shared word, add sequence number).
+ * All pointers are host pointers.  One mutex per handle (the reference's mMutex).
+ * Argument checks come before the device is touched; an otherwise valid call on a NULL handle
+ * answers ORB_E_NODEVICE where no device is visible (ORB_E_INVALID otherwise).
+ * Two deliberate deviations from the reference:
+ *  - DetectRelocalizationCandidates accepts any neighbour with mnRelocQuery == F->mnId (288-289)
+ *    and reads its mRelocScore even when that neighbour was not scored for this frame (a value
+ *    left by an earlier frame, or the uninitialised member).  Here a neighbour counts only if it
+ *    was scored in this query, the loop variant's rule: the call is a function of its inputs.
+ *  - the marking fields' initial value 0 aliasing a query id of 0 is not reproduced.
+ * ====================================================================== */
+typedef struct KeyFrameDatabase_t* KeyFrameDatabase_h;
+/* KeyFrameDatabase(const ORBVocabulary&) 32-36.  voc must outlive the database. */
+int KeyFrameDatabase_create(ORBvocabulary_h voc, KeyFrameDatabase_h* out);
+int KeyFrameDatabase_destroy(KeyFrameDatabase_h h);
+/* void add(KeyFrame*) 39-45: id = mnId (>= 0); word/value = mBowVec: words strictly ascending and
+ * below the vocabulary's word count; n <= 4096.  An id already present is ORB_E_INVALID (the
+ * reference would list it twice; no caller does).  Every add draws a new sequence number. */
+int KeyFrameDatabase_add(KeyFrameDatabase_h h, int32_t id, const uint32_t* word, const double* value, int n);
+/* `count` keyframes as CSR (start[0] = 0, keyframe i: [start[i], start[i+1])), added in index
+ * order (map load, tests).  All of them or none. */
+int KeyFrameDatabase_add_batch(KeyFrameDatabase_h h, int count, const int32_t* id, const int32_t* start,
+                               const uint32_t* word, const double* value);
+/* void erase(KeyFrame*) 47-67; an absent id is ORB_OK.  void clear() 69-73. */
+int KeyFrameDatabase_erase(KeyFrameDatabase_h h, int32_t id);
+int KeyFrameDatabase_clear(KeyFrameDatabase_h h);
+/* live keyframes and the BowVector entries they hold */
+int KeyFrameDatabase_size(KeyFrameDatabase_h h, int* n_keyframes, long long* n_entries);
+/* GetBestCovisibilityKeyFrames(10) of keyframe `id` as the accumulation step reads it (160, 277):
+ * the first n <= 10 of mvpOrderedConnectedKeyFrames.  Replaces the previous list (n = 0 drops it);
+ * ids need not be in the database.  The list belongs to the keyframe, not to its database entry:
+ * it may be set before add (LocalMapping updates connections before LoopClosing adds) and
+ * survives erase and clear. */
+int KeyFrameDatabase_set_covisibles(KeyFrameDatabase_h h, int32_t id, int n, const int32_t* ids);
+
+typedef struct orb_kfdb_query {
+    int nq;                      /* the query BowVector: nq <= 4096 words, strictly ascending */
+    const uint32_t* word;
+    const double* value;
+    int n_exclude;               /* loop: pKF->GetConnectedKeyFrames() (82); reloc: ignored */
+    const int32_t* exclude;
+    float minScore;              /* loop only */
+} orb_kfdb_query;
+typedef struct orb_kfdb_result {
+    int cap;                     /* capacity of cand */
+    int32_t* cand;               /* out: candidates in the reference's order */
+    int n_cand;                  /* out */
+    /* stage outputs, each pointer may be NULL: the scored subset (words > minCommonWords) in
+     * lKFsSharingWords order, capacity cap_scored */
+    int cap_scored;
+    int32_t* scored_id;
+    int32_t* scored_words;       /* mnLoopWords / mnRelocWords */
+    float* scored_score;         /* mLoopScore / mRelocScore */
+    float* scored_acc;           /* accScore of the entries that reached lScoreAndMatch, else NaN */
+    int n_scored, n_sharing, maxCommonWords, minCommonWords;   /* out */
+    float bestAccScore;          /* out (its initial value where there is no candidate) */
+} orb_kfdb_result;
+/* vector<KeyFrame*> DetectLoopCandidates(KeyFrame* pKF, float minScore) 76-197.
+ * ORB_E_CAPACITY when n_cand > cap or n_scored > cap_scored: the counts needed are set and
+ * nothing is written past a capacity.  L1_NORM vocabularies only (ORB_E_INVALID otherwise). */
+int KeyFrameDatabase_DetectLoopCandidates(KeyFrameDatabase_h h, const orb_kfdb_query* q, orb_kfdb_result* r);
+/* vector<KeyFrame*> DetectRelocalizationCandidates(Frame* F) 199-309 */
+int KeyFrameDatabase_DetectRelocalizationCandidates(KeyFrameDatabase_h h, const orb_kfdb_query* q,
+                                                    orb_kfdb_result* r);
+/* `count` frames against one database state in one launch set, one synchronisation */
+int KeyFrameDatabase_DetectRelocalizationCandidates_batch(KeyFrameDatabase_h h, int count,
+                                                          const orb_kfdb_query* q, orb_kfdb_result* r);
+/* Measurement (no reference counterpart): ms3 = {share count and selection, scoring, whole call}
+ * of the last timed query; the first two are HIP-event times, the third is host wall time. */
+int KeyFrameDatabase_enable_timing(KeyFrameDatabase_h h, int on);
+int KeyFrameDatabase_last_timings(KeyFrameDatabase_h h, float* ms3);
+
 /* DBoW2::FeatureVector (std::map<NodeId, std::vector<unsigned>>) as CSR: strictly ascending
  * node ids, the feature indices of node a at feat[start[a] .. start[a+1]) in insertion order.
  * (Computed by the caller's vocabulary; ORBvoc.txt is not shipped with the reference.) */
@@ -1118,6 +1195,11 @@ int orbgpu_unit_essgraph_stage(const essgraph_problem* P, double lambda, essgrap
 /* Test knob: the pose graph's dense single-workgroup solver takes systems of at most `rows` rows
  * (default and maximum 144); 0 sends every system to the block-sparse solver.  Process-wide. */
 int orbgpu_unit_set_ess_dense_max(int rows);
+/* Test knob: a KeyFrameDatabase created from now on starts with room for `slots` keyframes and
+ * `entries` BowVector entries (defaults 1024 and 1 << 20; both double when full, and the entry
+ * pool is compacted when its holes exceed its live entries); 0 restores a default.  Returns 1 on
+ * a negative value.  Process-wide, host-side. */
+int orbgpu_unit_set_kfdb_initial_capacity(int slots, int entries);
 /* Instrumented builds only (make prof): read and clear the BA/pose section timers (32 x u64
  * clock64 deltas of workgroup 0); ORB_E_INVALID in normal builds. */
 int orbgpu_debug_prof(unsigned long long* out32);
