@@ -4,7 +4,7 @@ Host mirror (Python, over the C ABI of include/orbslam_gpu.h) of the reference
 junejunejune/c_orb_slam classes on the hot path.  All compute runs in the HIP
 library liborbslam_gpu.so (gfx950); there is no CPU fallback.
 """
-from ._lib import KP_DTYPE, OrbGpuError, device_available, lib  # noqa: F401
+from ._lib import KP_DTYPE, ORB_DEPTH_F32, ORB_DEPTH_U16, OrbGpuError, device_available, lib  # noqa: F401
 from .orb import FeatureVector, Frame, MapPoints, ORBextractor, ORBmatcher  # noqa: F401
 from .optimizer import (BundleAdjustment, LocalBundleAdjustment, OptimizeEssentialGraph,  # noqa: F401
                         OptimizeSim3, OptimizeSim3Batch, PoseOptimization, PoseOptimizationBatch)

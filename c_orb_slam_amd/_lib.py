@@ -137,6 +137,7 @@ def lib():
     L.ORBextractor_extract.argtypes = [vp, vp, i32, i32, i32, vp, vp, i32, P(i32)]
     L.ORBextractor_extract_batch.argtypes = [vp, vp, i32, i32, i32, i32, sz, i32, vp, vp, i32, i32, vp]
     L.ORBextractor_extract_images.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp]
+    L.ORBextractor_cvtColor_batch.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, sz, i32, vp, i32, sz]
     L.ORBextractor_get_level.argtypes = [vp, i32, i32, vp, i32, P(i32), P(i32)]
     L.ORBextractor_get_blurred_level.argtypes = [vp, i32, i32, vp, i32, P(i32), P(i32)]
     L.ORBextractor_get_levels.argtypes = [vp, P(i32), P(f32)]
@@ -228,6 +229,8 @@ def lib():
     L.Frame_UndistortKeyPoints.argtypes = [vp, vp]
     L.Frame_UndistortKeyPoints_batch.argtypes = [vp, i32, vp]
     L.Frame_ComputeImageBounds.argtypes = [vp, i32, i32, vp, vp, i32, vp]
+    L.Frame_ComputeStereoFromRGBD.argtypes = [vp, vp, vp]
+    L.Frame_ComputeStereoFromRGBD_batch.argtypes = [vp, i32, vp, vp]
     L.ORBvocabulary_create.argtypes = [P(vp)]
     L.ORBvocabulary_destroy.argtypes = [vp]
     L.ORBvocabulary_loadFromTextFile.argtypes = [vp, C.c_char_p]
@@ -330,6 +333,16 @@ class orb_unproject(C.Structure):
 class orb_undistort(C.Structure):
     _fields_ = [("N", C.c_int), ("keys", C.c_void_p), ("keysUn", C.c_void_p), ("K", C.c_float * 9),
                 ("dist", C.c_float * 8), ("ndist", C.c_int)]
+
+
+ORB_DEPTH_U16, ORB_DEPTH_F32 = 0, 1
+
+
+class orb_rgbd(C.Structure):
+    _fields_ = [("N", C.c_int), ("keys", C.c_void_p), ("keysUn", C.c_void_p), ("depth", C.c_void_p),
+                ("depth_type", C.c_int), ("cols", C.c_int), ("rows", C.c_int), ("step", C.c_size_t),
+                ("depthMapFactor", C.c_float), ("mbf", C.c_float), ("uRight", C.c_void_p),
+                ("depth_out", C.c_void_p)]
 
 
 class orb_bow(C.Structure):

@@ -105,6 +105,10 @@ public:
     int extract(const uint8_t* imgs, int B, int W, int H, int step, size_t img_stride, bool imgs_on_device,
                 orb_kp* kps, uint8_t* desc, int cap, bool out_on_device, int* n_out,
                 const uint8_t* const* list = nullptr);
+    // Tracking::GrabImage*'s cvtColor over B colour images (frame_input.hip), enqueued on stream():
+    // host `src` goes through the pinned staging block extract() uses; `gray` is device memory
+    int cvt_color(const uint8_t* src, int B, int W, int H, int channels, int rgb, int step, size_t img_stride,
+                  bool src_on_device, uint8_t* gray, int gray_step, size_t gray_stride);
     int get_level(int index, int level, uint8_t* dst, int dst_step, int* w, int* h);
     int get_blurred(int index, int level, uint8_t* dst, int dst_step, int* w, int* h);
     int timings(float* ms6);

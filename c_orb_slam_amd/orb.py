@@ -78,6 +78,44 @@ class ORBextractor:
               "ORBextractor_extract_batch(device)")
         return n
 
+    def cvtColor_device(self, src_ptr, B, W, H, channels, rgb, step, img_stride, d_gray_ptr, gray_step,
+                        gray_stride, src_on_device=True):
+        """cv::cvtColor(im, im, CV_{RGB,BGR,RGBA,BGRA}2GRAY) of Tracking::GrabImage* (mbRGB = rgb) for B
+        colour images, enqueued on this extractor's stream: raw pointers as extract_device takes them
+        (src a device address, or a host address with src_on_device=False); the grey images are
+        always device memory, so extract_device on this extractor can follow without a wait."""
+        check(self._L.ORBextractor_cvtColor_batch(self._h, C.c_void_p(src_ptr), int(B), int(W), int(H),
+                                                  int(channels), int(bool(rgb)), int(step), int(img_stride),
+                                                  int(bool(src_on_device)), C.c_void_p(d_gray_ptr), int(gray_step),
+                                                  int(gray_stride)), "ORBextractor_cvtColor_batch")
+
+    def extract_color(self, image, rgb):
+        """GrabImage* on a colour frame: cvtColor (H x W x 3 or H x W x 4 host array, mbRGB = rgb) on
+        the GPU, then operator() on the grey image it leaves in HBM.  Returns what __call__ returns."""
+        import torch
+        img = np.asarray(image)
+        if img.ndim != 3 or img.shape[2] not in (3, 4) or img.dtype != np.uint8:
+            raise ValueError("extract_color takes an H x W x 3 or H x W x 4 uint8 image")
+        img = np.ascontiguousarray(img)
+        if img.size == 0:
+            return np.zeros(0, KP_DTYPE), None
+        H, W, ch = img.shape
+        gray = torch.empty((H, W), dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
+        self.cvtColor_device(img.ctypes.data, 1, W, H, ch, rgb, img.strides[0], img.strides[0] * H, gray.data_ptr(),
+                             W, W * H, src_on_device=False)
+        while True:
+            kps = np.zeros(self._cap, KP_DTYPE)
+            desc = np.zeros((self._cap, 32), np.uint8)
+            n = np.zeros(1, np.int32)
+            rc = self._L.ORBextractor_extract_batch(self._h, C.c_void_p(gray.data_ptr()), 1, W, H, W, W * H, 1,
+                                                    ptr(kps), ptr(desc), self._cap, 0, ptr(n))
+            if rc == ORB_E_CAPACITY:
+                self._cap *= 2
+                continue
+            check(rc, "ORBextractor_extract_batch(grey on device)")
+            n = int(n[0])
+            return kps[:n].copy(), (desc[:n].copy() if n else None)
+
     def extract_host_to_device(self, image, d_kps_ptr, d_desc_ptr, cap):
         """operator() on a host (pageable) image, keypoints and descriptors left in HBM for the
         device-resident tracking calls: the H2D copy of the image is part of the call.  -> count."""
@@ -515,6 +553,88 @@ class ORBmatcher:
             check(self._L.Frame_UndistortKeyPoints_batch(self._h, len(us), arr), "Frame_UndistortKeyPoints_batch")
         finally:
             check(self._L.ORBmatcher_set_device_pointers(self._h, 0))
+
+    @staticmethod
+    def _depth_type(dtype):
+        from ._lib import ORB_DEPTH_F32, ORB_DEPTH_U16
+        name = str(dtype).replace("torch.", "")
+        if name == "uint16":
+            return ORB_DEPTH_U16
+        if name == "float32":
+            return ORB_DEPTH_F32
+        raise ValueError("the depth image is uint16 (as the driver loads a 16-bit PNG) or float32")
+
+    def ComputeStereoFromRGBD(self, keys, keysUn, depth, depthMapFactor, mbf):
+        """Frame::ComputeStereoFromRGBD with GrabImageRGBD's convertTo(CV_32F, mDepthMapFactor) folded
+        in: keys / keysUn (KP_DTYPE) are mvKeys / mvKeysUn, depth the rows x cols image as loaded
+        (uint16 or float32; its row stride is kept).  -> (mvuRight, mvDepth, keypoints with depth)."""
+        from ._lib import orb_rgbd
+        keys = np.ascontiguousarray(keys, KP_DTYPE)
+        keysUn = np.ascontiguousarray(keysUn, KP_DTYPE)
+        if len(keys) != len(keysUn):
+            raise ValueError("mvKeys and mvKeysUn differ in length")
+        depth = np.asarray(depth)
+        if depth.ndim != 2:
+            raise ValueError("the depth image is rows x cols")
+        typ = self._depth_type(depth.dtype)
+        if depth.size and (depth.strides[1] != depth.itemsize or depth.strides[0] < depth.shape[1] * depth.itemsize):
+            depth = np.ascontiguousarray(depth)
+        N = len(keys)
+        uR = np.zeros(max(N, 1), np.float32)
+        dep = np.zeros(max(N, 1), np.float32)
+        n = C.c_int()
+        q = orb_rgbd(N, keys.ctypes.data if N else None, keysUn.ctypes.data if N else None,
+                     depth.ctypes.data if depth.size else None, typ, depth.shape[1], depth.shape[0],
+                     depth.strides[0] if depth.size else depth.shape[1] * depth.itemsize, float(depthMapFactor),
+                     float(mbf), uR.ctypes.data, dep.ctypes.data)
+        check(self._L.Frame_ComputeStereoFromRGBD(self._h, C.byref(q), C.byref(n)), "Frame_ComputeStereoFromRGBD")
+        return uR[:N], dep[:N], n.value
+
+    def ComputeStereoFromRGBD_device(self, frames, deferred=False):
+        """The batch form over device-resident frames, enqueued on this matcher's stream: frames[f] =
+        dict(keys, keysUn (torch device tensors, N x 7 words), depth (rows x cols torch device tensor,
+        uint16 or float32, any row stride), depthMapFactor, mbf, uRight, depth_out (N f32, out)).
+        -> ndepth (int32 numpy, one per frame).  deferred=True queues the call in a deferred chain
+        (ORBmatcher_set_deferred) and returns (ndepth, finish): the matcher stays in device mode, and
+        the counts land in ndepth when finish() closes the chain (ORBmatcher_finish)."""
+        from ._lib import orb_rgbd
+        qs = []
+        for f in frames:
+            d = f["depth"]
+            if d.dim() != 2 or (d.numel() and d.stride(1) != 1):
+                raise ValueError("the depth image is rows x cols with unit column stride")
+            es = d.element_size()
+            qs.append(orb_rgbd(int(f["keys"].shape[0]), f["keys"].data_ptr(), f["keysUn"].data_ptr(), d.data_ptr(),
+                               self._depth_type(d.dtype), int(d.shape[1]), int(d.shape[0]),
+                               int(d.stride(0)) * es if d.numel() else int(d.shape[1]) * es,
+                               float(f["depthMapFactor"]), float(f["mbf"]), f["uRight"].data_ptr(),
+                               f["depth_out"].data_ptr()))
+        arr = (orb_rgbd * max(len(qs), 1))(*qs)
+        nd = np.zeros(max(len(qs), 1), np.int32)
+        check(self._L.ORBmatcher_set_device_pointers(self._h, 1))
+        queued = False
+        try:
+            if deferred:
+                check(self._L.ORBmatcher_set_deferred(self._h, 1))
+            check(self._L.Frame_ComputeStereoFromRGBD_batch(self._h, len(qs), arr, ptr(nd)),
+                  "Frame_ComputeStereoFromRGBD_batch")
+            queued = deferred
+        finally:
+            if not queued:   # a deferred chain keeps the matcher in device mode until finish()
+                if deferred:
+                    self._L.ORBmatcher_set_deferred(self._h, 0)
+                check(self._L.ORBmatcher_set_device_pointers(self._h, 0))
+        if not deferred:
+            return nd[:len(qs)]
+
+        def finish():
+            try:
+                check(self._L.ORBmatcher_finish(self._h), "ORBmatcher_finish")
+            finally:
+                self._L.ORBmatcher_set_deferred(self._h, 0)
+                check(self._L.ORBmatcher_set_device_pointers(self._h, 0))
+            return nd[:len(qs)]
+        return nd[:len(qs)], finish
 
     def ComputeImageBounds(self, cols, rows, K, dist):
         """Frame::ComputeImageBounds (Frame.cc:436-464) + the grid factors (Frame.cc:155-156) ->

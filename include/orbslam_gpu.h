@@ -88,6 +88,24 @@ int ORBextractor_extract_images(ORBextractor_h h, const uint8_t* const* imgs, in
                                 int height, int step, orb_kp* kps, uint8_t* desc, int cap_per_image,
                                 int outputs_on_device, int* n_out);
 
+/* cv::cvtColor(im, im, CV_RGB2GRAY | CV_BGR2GRAY | CV_RGBA2GRAY | CV_BGRA2GRAY) as
+ * Tracking::GrabImageStereo / GrabImageRGBD / GrabImageMonocular apply it to a 3- or 4-channel
+ * image (mbRGB picks the order) before the Frame is built.  OpenCV 3.2's 8-bit path: per pixel
+ * (R*4899 + G*9617 + B*1868 + 8192) >> 14 in integers, alpha ignored; "parity unpinned" at this
+ * OpenCV call site.  rgb != 0: the first byte of a pixel is R, otherwise B.
+ * `batch` images of equal size, image b at src + b*img_stride (rows `step` >= width*channels
+ * bytes apart; src_on_device != 0: a device pointer, otherwise host memory that is staged through
+ * the extractor's pinned block as ORBextractor_extract_images stages its images).  The result is
+ * always a device image: grey image b at gray_dev + b*gray_stride, rows gray_step >= width bytes
+ * apart; no alignment is required of either side, and the images of a batch may not overlap
+ * (batch <= 65535).  The call is enqueued on ORBextractor_stream(h)
+ * and does not wait: a following ORBextractor_extract_batch(h, gray_dev, ..., imgs_on_device = 1,
+ * ...) on the same handle sees the grey images.  channels = 3 or 4 (the reference makes no call
+ * for a 1-channel image: ORB_E_INVALID); width, height or batch 0: ORB_OK, nothing is done. */
+int ORBextractor_cvtColor_batch(ORBextractor_h h, const uint8_t* src, int batch, int width, int height,
+                                int channels, int rgb, int step, size_t img_stride, int src_on_device,
+                                uint8_t* gray_dev, int gray_step, size_t gray_stride);
+
 /* mvImagePyramid[level] (ORBextractor.h:85) of image `index` of the last call,
  * copied to host WITH its 19-px REFLECT_101 border (Frame.cc:573-580 reads it).
  * dst must hold (w+38)*(h+38) bytes at stride dst_step; *w,*h = unpadded dims. */
@@ -344,6 +362,44 @@ int Frame_UndistortKeyPoints_batch(ORBmatcher_h h, int count, const orb_undistor
  * With distortion the four image corners go through the UndistortKeyPoints kernel. */
 int Frame_ComputeImageBounds(ORBmatcher_h h, int cols, int rows, const float* K, const float* dist, int ndist,
                              float* bounds);
+
+/* void Frame::ComputeStereoFromRGBD(const cv::Mat& imDepth), with the depth conversion that
+ * Tracking::GrabImageRGBD applies in front of it folded in.  Per keypoint i:
+ *   u = (int)keys[i].pt.x, v = (int)keys[i].pt.y   (C++ truncation, as imDepth.at<float>(v, u)
+ *                                                   converts its float arguments);
+ *   raw = depth pixel (v, u);  d = (float)raw * depthMapFactor when the reference converts, i.e.
+ *   when fabs(depthMapFactor - 1.0f) > 1e-5 or depth_type != ORB_DEPTH_F32 (cv::Mat::convertTo(
+ *   CV_32F, scale): one float multiply), otherwise d = raw untouched;
+ *   d > 0:  depth_out[i] = d, uRight[i] = keysUn[i].pt.x - mbf / d;  otherwise both are -1
+ *   (NaN has no depth; +inf gives uRight = keysUn[i].pt.x).
+ * The float depth image is never built: N pixels are read, not cols*rows.  One deliberate
+ * difference from the reference: a keypoint whose (v, u) lies outside [0, rows) x [0, cols) gets
+ * -1 / -1 (the reference would read out of bounds).  ndepth (may be NULL): ndepth[f] = the
+ * keypoints of frame f with depth, which Tracking::StereoInitialization tests against 500.
+ * Pointer space per ORBmatcher_set_device_pointers, as for Frame_UndistortKeyPoints_batch /
+ * ORBmatcher_ComputeStereoMatches_batch: device arrays are enqueued on ORBmatcher_stream and
+ * ndepth is read back with the matcher's counts (inside a deferred chain it lands at
+ * ORBmatcher_finish); host arrays (keys and the depth image included) are staged, and the
+ * results copied back and waited for.  ORB_E_INVALID: N < 0, a null pointer with N > 0, an
+ * unknown depth_type, negative cols / rows, step smaller than a row. */
+#define ORB_DEPTH_U16 0
+#define ORB_DEPTH_F32 1
+typedef struct orb_rgbd {
+    int N;
+    const orb_kp* keys;          /* mvKeys (distorted): picks the depth pixel */
+    const orb_kp* keysUn;        /* mvKeysUn: kpU.pt.x of mvuRight */
+    const void* depth;           /* imD as the driver loaded it, before convertTo */
+    int depth_type;              /* ORB_DEPTH_U16 / ORB_DEPTH_F32 */
+    int cols, rows;
+    size_t step;                 /* bytes per row */
+    float depthMapFactor;        /* Tracking::mDepthMapFactor (already 1/DepthMapFactor, or 1) */
+    float mbf;
+    float* uRight;               /* out: mvuRight (N), -1 = no depth */
+    float* depth_out;            /* out: mvDepth (N), -1 = no depth */
+} orb_rgbd;
+int Frame_ComputeStereoFromRGBD_batch(ORBmatcher_h h, int count, const orb_rgbd* R, int* ndepth);
+/* One frame: the batch form with count = 1. */
+int Frame_ComputeStereoFromRGBD(ORBmatcher_h h, const orb_rgbd* R, int* ndepth);
 
 /* New MapPoints from a stereo frame (Tracking::StereoInitialization / CreateNewKeyFrame /
  * UpdateLastFrame, Tracking.cc:520-560, 1025-1080, 837-860): for every keypoint with depth > 0,
