@@ -250,6 +250,7 @@ def lib():
     L.Frame_isInFrustum_batch.argtypes = [vp, i32, vp, vp, f32, f32, vp, vp, vp, vp, vp, vp, vp]
     L.ORBmatcher_enable_timing.argtypes = [vp, i32]
     L.ORBmatcher_last_timings.argtypes = [vp, vp, vp]
+    L.ORBmatcher_last_search_plan.argtypes = [vp, vp]
     L.orbgpu_unit_ldlt_factor.argtypes = [i32, vp, vp]
     L.orbgpu_unit_wave_tree.argtypes = [vp, vp]
     L.orbgpu_unit_shared_div.argtypes = [vp, vp, i32, vp]

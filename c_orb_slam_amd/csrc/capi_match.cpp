@@ -133,6 +133,11 @@ int ORBmatcher_last_timings(ORBmatcher_h h, float* ms8, long long* counts8) {
     return h->m->timings(ms8, counts8) ? ORB_E_HIP : ORB_OK;
 }
 
+int ORBmatcher_last_search_plan(ORBmatcher_h h, int out[6]) {
+    if (!h || !out) return ORB_E_INVALID;
+    return h->m->last_plan(out) ? ORB_E_INVALID : ORB_OK;
+}
+
 // ORBmatcher.cc:1647-1663 (SWAR popcount == popcount)
 int ORBmatcher_DescriptorDistance(const uint8_t* a, const uint8_t* b) {
     if (!a || !b) return ORB_E_INVALID;
@@ -157,7 +162,9 @@ int ORBmatcher_SearchByProjection_LastFrame_batch(ORBmatcher_h h, int npairs, co
     const bool dev = m->device_pointers();
     hipStream_t s = m->stream();
     for (int p = 0; p < npairs; p++) {
-        if (!frame_ok(&cur[p]) || !last[p].Tcw || last[p].N < 0 || (last[p].N > 0 && !last[p].keysUn)) return ORB_E_INVALID;
+        if (!frame_ok(&cur[p]) || !last[p].Tcw || last[p].N < 0 || last[p].N > orbgpu::kMaxFrameKeys ||
+            (last[p].N > 0 && !last[p].keysUn))
+            return ORB_E_INVALID;
         if (last[p].N > 0 && (!last_keys[p] || !last_mp[p] || !last_outlier[p])) return ORB_E_INVALID;
         if (mps[p].n > 0 && (!mps[p].pos || !mps[p].desc || !mps[p].observations)) return ORB_E_INVALID;
         if (!dev) {  // host mode: validate map point indices (device mode trusts the caller)

@@ -1168,6 +1168,8 @@ int Matcher::run(std::vector<SearchDev>& probs, float th, bool bMono, bool lastM
     const bool vis = frustum_ != nullptr;   // SearchLocalPoints: in-view query lists
     for (auto& p : probs) {
         if (p.cur.N > kMaxFrameKeys || p.cur.N < 0 || p.nq < 0) return -1;
+        // LastFrame: k_select_r's rotation check covers the register slots only (512 * kSelQLast)
+        if (lastMode && p.nq > kMaxFrameKeys) return -1;
         maxN = std::max(maxN, p.cur.N);
         need += ((size_t)(kGridCells + 1 + p.cur.N) * 4 + 255) & ~(size_t)255;
         need += ((size_t)p.nq * (kTopK * 8 + 16 + 8) + 255) & ~(size_t)255;
@@ -1224,12 +1226,20 @@ int Matcher::run(std::vector<SearchDev>& probs, float th, bool bMono, bool lastM
     }
     hipLaunchKernelGGL(k_build_grid, dim3(np), dim3(256), grid_lds_bytes(maxN), stream_, dp, 1);
     mark(1);
+    // the launch choice, recorded for last_plan(): the candidate search stages the frame in LDS when
+    // every frame of the batch fits (and local search has not opted out), in 1024- or 256-thread
+    // workgroups; the unstaged search runs 256 threads
+    const bool staged = maxN <= kStageMaxN && (lastMode || cand_local_stage());
+    const int candNT = maxq > 0 ? (staged ? stage_threads() : 256) : 0;
+    const int selNT = maxq > 0 ? (lastMode ? 512 : select_local_threads()) : 0;
+    const int plan[6] = {staged && maxq > 0, candNT, selNT, maxN, maxq, np};
+    std::memcpy(plan_, plan, sizeof(plan_));
     if (maxq > 0) {
         if (lastMode) {
-            if (maxN <= kStageMaxN && stage_threads() == 256)
+            if (staged && candNT == 256)
                 hipLaunchKernelGGL((k_candidates<true, true, 256>), cand_grid(maxq, 256, np), dim3(256), kStageLds,
                                    stream_, dp, np, cand_gx(maxq, 256), th, (int)bMono, counters());
-            else if (maxN <= kStageMaxN)
+            else if (staged)
                 hipLaunchKernelGGL((k_candidates<true, true, kStageThreads>), cand_grid(maxq, kStageThreads, np),
                                    dim3(kStageThreads), kStageLds,
                                    stream_, dp, np, cand_gx(maxq, kStageThreads), th, (int)bMono, counters());
@@ -1241,10 +1251,10 @@ int Matcher::run(std::vector<SearchDev>& probs, float th, bool bMono, bool lastM
             hipLaunchKernelGGL((k_select_r<true, 512, kSelQLast>), dim3(np), dim3(512), select_lds_bytes(maxN), stream_, dp,
                                th, (int)bMono, nnratio, (int)checkOri_, maxN);
         } else {
-            if (maxN <= kStageMaxN && cand_local_stage() && stage_threads() == 256)
+            if (staged && candNT == 256)
                 hipLaunchKernelGGL((k_candidates<false, true, 256>), cand_grid(maxq, 256, np), dim3(256), kStageLds,
                                    stream_, dp, np, cand_gx(maxq, 256), th, 0, counters());
-            else if (maxN <= kStageMaxN && cand_local_stage())
+            else if (staged)
                 hipLaunchKernelGGL((k_candidates<false, true, kStageThreads>), cand_grid(maxq, kStageThreads, np),
                                    dim3(kStageThreads), kStageLds,
                                    stream_, dp, np, cand_gx(maxq, kStageThreads), th, 0, counters());
@@ -1254,7 +1264,7 @@ int Matcher::run(std::vector<SearchDev>& probs, float th, bool bMono, bool lastM
             mark(2);
             // SearchLocalPoints-sized query sets (thousands of local map points, long occupancy
             // chains between duplicated points): 16 waves per round of the fixed point
-            if (select_local_threads() == 512)
+            if (selNT == 512)
                 hipLaunchKernelGGL((k_select_r<false, 512, 2 * kSelQLocal>), dim3(np), dim3(512), select_lds_bytes(maxN),
                                    stream_, dp, th, 0, nnratio, 0, maxN);
             else
@@ -1262,6 +1272,15 @@ int Matcher::run(std::vector<SearchDev>& probs, float th, bool bMono, bool lastM
                                    dim3(kSelectLocalThreads), select_lds_bytes(maxN), stream_, dp, th, 0, nnratio, 0, maxN);
         }
     } else {
+        // no problem has a query: k_select_r, which writes the counts, does not run.  The callers
+        // keep the counts of a batch in one array: one memset, unless a problem's slot lies elsewhere
+        bool contiguous = true;
+        for (int k = 0; k < np; k++) contiguous = contiguous && probs[k].nmatches == probs[0].nmatches + k;
+        if (contiguous) {
+            ORB_HIP_CHECK(hipMemsetAsync(probs[0].nmatches, 0, sizeof(int) * np, stream_));
+        } else {
+            for (auto& p : probs) ORB_HIP_CHECK(hipMemsetAsync(p.nmatches, 0, sizeof(int), stream_));
+        }
         mark(2);
     }
     mark(3);

@@ -146,6 +146,13 @@ public:
         ORB_HIP_CHECK(hipStreamSynchronize(stream_));
         return 0;
     }
+    // what the last run() launched (ORBmatcher_last_search_plan): staged, candidate workgroup
+    // threads, selection workgroup threads, maxN, maxq, np; nonzero before the first run()
+    int last_plan(int out[6]) const {
+        if (plan_[5] < 0) return -1;
+        for (int i = 0; i < 6; i++) out[i] = plan_[i];
+        return 0;
+    }
     float nnratio() const { return nnratio_; }
     bool check_ori() const { return checkOri_; }
 
@@ -188,6 +195,7 @@ private:
     void* d_dense_ = nullptr;
     size_t dense_cap_ = 0;
     bool timing_ = false;
+    int plan_[6] = {0, 0, 0, 0, 0, -1};
     const FrustumDev* frustum_ = nullptr;   // pending k_frustum of search_local_points
     float frustumCos_ = 0.5f, frustumLsf_ = 0.f;
     hipEvent_t ev_[16] = {};

@@ -351,6 +351,35 @@ class ORBmatcher:
               "SearchByProjection(LastFrame)")
         return n.value
 
+    def SearchByProjection_LastFrame_batch(self, curs, cur_mps, lasts, last_keys, last_mps, last_outliers, mpss,
+                                           th, bMono):
+        """ORBmatcher_SearchByProjection_LastFrame_batch: the search above for len(curs) independent
+        (cur, last) pairs in one set of launches (host arrays); cur_mps[p] updated in place.
+        -> nmatches (int32 array, one per pair)."""
+        n = len(curs)
+        for c, F in zip(cur_mps, curs):
+            assert c.dtype == np.int32 and c.flags.c_contiguous and len(c) == F.N
+        lk = [np.ascontiguousarray(k, KP_DTYPE) for k in last_keys]
+        lm = [np.ascontiguousarray(m, np.int32) for m in last_mps]
+        lo = [np.ascontiguousarray(o, np.uint8) for o in last_outliers]
+        cnt = max(n, 1)
+        cf = (orb_frame * cnt)(*[F.cstruct() for F in curs])
+        lf = (orb_frame * cnt)(*[F.cstruct() for F in lasts])
+        mp = (orb_mappoints * cnt)(*[m.cstruct() for m in mpss])
+        arr = lambda xs: (C.c_void_p * cnt)(*[x.ctypes.data for x in xs])
+        nm = np.zeros(cnt, np.int32)
+        check(self._L.ORBmatcher_SearchByProjection_LastFrame_batch(self._h, n, cf, arr(cur_mps), lf, arr(lk), arr(lm),
+                                                                    arr(lo), mp, float(th), int(bool(bMono)), ptr(nm)),
+              "SearchByProjection(LastFrame) batch")
+        return nm[:n]
+
+    def last_search_plan(self):
+        """ORBmatcher_last_search_plan (test-only): what the last guided search launched ->
+        dict(staged, cand_threads, select_threads, max_n, max_q, np)."""
+        out = np.zeros(6, np.int32)
+        check(self._L.ORBmatcher_last_search_plan(self._h, ptr(out)), "ORBmatcher_last_search_plan")
+        return dict(zip(("staged", "cand_threads", "select_threads", "max_n", "max_q", "np"), (int(v) for v in out)))
+
     def SearchByProjection_MapPoints(self, F: Frame, cur_mp, track_in_view, proj_x, proj_xr, proj_y, level,
                                      view_cos, mp_index, mps: MapPoints, th=1.0):
         """SearchByProjection(F, vpMapPoints, th) (ORBmatcher.cc:45); cur_mp updated in place."""

@@ -168,6 +168,17 @@ void* ORBmatcher_stream(ORBmatcher_h h);
  *   counts8[7]: ComputeStereoMatches left keypoints whose 11x11 SAD windows were read. */
 int ORBmatcher_enable_timing(ORBmatcher_h h, int on);
 int ORBmatcher_last_timings(ORBmatcher_h h, float* ms8, long long* counts8);
+/* Test-only, read-only: which launches the last guided search of `h` chose
+ * (ORBmatcher_SearchByProjection_LastFrame[_batch], ORBmatcher_SearchByProjection_MapPoints,
+ * ORBmatcher_SearchLocalPoints_batch).  out[0]: 1 the candidate search staged the frame in LDS,
+ * 0 it walked the grid in device memory (a frame of the batch above 1536 keypoints, or
+ * ORBGPU_CAND_LOCAL_STAGE=0); out[1]: threads per candidate workgroup (1024, or 256 unstaged or
+ * with ORBGPU_CAND_NT=256); out[2]: threads per selection workgroup (512 last-frame, 1024 local,
+ * 512 local with ORBGPU_SELECT_LOCAL_NT=512); out[1] = out[2] = 0 when no problem had a query
+ * (nothing but the grid build ran); out[3]: the largest frame keypoint count of the batch;
+ * out[4]: the largest query count; out[5]: the number of problems.  Host state only.
+ * ORB_E_INVALID before the first search that reached its launches. */
+int ORBmatcher_last_search_plan(ORBmatcher_h h, int out[6]);
 /* Deferred completion (no reference counterpart; the reference's calls are synchronous).
  * With deferred on (device-pointer matchers only), the device-resident batch calls
  * ORBmatcher_ComputeStereoMatches_batch, MapPoint_CreateStereo_batch_device,
@@ -221,7 +232,8 @@ typedef struct orb_mappoints {
  * last_outlier[i]: LastFrame.mvbOutlier; last_keys: LastFrame.mvKeys (octave),
  * last_keysUn: LastFrame.mvKeysUn (angle).
  * cur_mp (in/out, N of current): CurrentFrame.mvpMapPoints as indices (-1 = NULL).
- * *nmatches = return value of the reference. */
+ * *nmatches = return value of the reference (0 when the last frame has no keypoint).
+ * Both frames hold at most 4096 keypoints: ORB_E_INVALID above, with nothing written. */
 int ORBmatcher_SearchByProjection_LastFrame(ORBmatcher_h h, const orb_frame* cur, int32_t* cur_mp,
                                             const orb_frame* last, const orb_kp* last_keys,
                                             const int32_t* last_mp, const uint8_t* last_outlier,

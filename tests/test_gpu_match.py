@@ -111,8 +111,6 @@ def test_search_candidates_csr(gpu):
 
 
 def test_batched_pairs_equal_single(gpu, kitti_frames):
-    import ctypes as C
-    from c_orb_slam_amd._lib import lib, ptr, KP_DTYPE
     frames, Hs, Rs, res, scale = kitti_frames
     K4 = synthetic.intrinsics(1241, 376)
     probs = []
@@ -126,19 +124,10 @@ def test_batched_pairs_equal_single(gpu, kitti_frames):
         g = np.full(cur.N, -1, np.int32)
         n = m.SearchByProjection_LastFrame(cur, g, last, k0, lm, lo, mps, 15.0, True)
         singles.append((n, g))
-    # batch call through the C ABI
-    from c_orb_slam_amd._lib import orb_frame, orb_mappoints
-    curs = (orb_frame * 2)(*[p[0][0].cstruct() for p in probs])
-    lasts = (orb_frame * 2)(*[p[0][1].cstruct() for p in probs])
-    mpss = (orb_mappoints * 2)(*[p[0][2].cstruct() for p in probs])
     outs = [np.full(p[0][0].N, -1, np.int32) for p in probs]
-    lks = [np.ascontiguousarray(p[1], KP_DTYPE) for p in probs]
-    arr = lambda xs: (C.c_void_p * 2)(*[x.ctypes.data for x in xs])
-    nm = np.zeros(2, np.int32)
-    rc = lib().ORBmatcher_SearchByProjection_LastFrame_batch(m._h, 2, curs, arr(outs), lasts, arr(lks),
-                                                             arr([p[0][3] for p in probs]),
-                                                             arr([p[0][4] for p in probs]), mpss, 15.0, 1, ptr(nm))
-    assert rc == 0
+    nm = m.SearchByProjection_LastFrame_batch([p[0][0] for p in probs], outs, [p[0][1] for p in probs],
+                                              [p[1] for p in probs], [p[0][3] for p in probs],
+                                              [p[0][4] for p in probs], [p[0][2] for p in probs], 15.0, True)
     for p in range(2):
         assert nm[p] == singles[p][0] and np.array_equal(outs[p], singles[p][1])
 

@@ -14,6 +14,7 @@ import pytest
 import oracle_lib
 from c_orb_slam_amd import synthetic
 from c_orb_slam_amd.orb import Frame
+from match_cases import local_map
 
 pytestmark = pytest.mark.gpu
 
@@ -26,41 +27,6 @@ def seq(gpu):
     ex = gpu.ORBextractor(1200, 1.2, 8, 20, 7, max_width=W, max_height=H, max_batch=4)
     res = ex.extract_batch(frames)
     return Rs, res, ex.GetScaleFactors()
-
-
-def local_map(rng, kps, desc, scale, Twc=np.eye(4, dtype=np.float32), extra=300):
-    """Map points lifted from a keyframe's keypoints (world = that frame's camera, then Twc), with
-    the MapPoint fields UpdateNormalAndDepth sets (MapPoint.cc:349-371), plus points that fail
-    each isInFrustum test."""
-    fx, fy, cx, cy = synthetic.intrinsics(W, H)
-    n = len(kps)
-    d = rng.uniform(4.0, 60.0, n)
-    Xc = np.stack([(kps["x"] - cx) / fx * d, (kps["y"] - cy) / fy * d, d], 1)
-    oct_ = kps["octave"].astype(int)
-    # extras: behind the camera, far outside the image, scale-invariance misses, oblique normals
-    e = rng.integers(0, 4, extra)
-    Xe = rng.normal(0, 1, (extra, 3)) * [10, 5, 20]
-    Xe[e == 0, 2] = -np.abs(Xe[e == 0, 2]) - 1
-    Xe[e == 1, :2] *= 50
-    Xe[e >= 2, 2] = np.abs(Xe[e >= 2, 2]) + 5
-    X = np.vstack([Xc, Xe])
-    oct_all = np.concatenate([oct_, rng.integers(0, 8, extra)])
-    dist = np.linalg.norm(X, axis=1)
-    mx = dist * scale[oct_all]
-    mx[n:][e[:] == 2] *= rng.choice([0.3, 3.0], int((e == 2).sum()))      # outside [0.8 min, 1.2 max]
-    mn = mx / scale[7]
-    nrm = X / dist[:, None]
-    tilt = np.where(np.concatenate([rng.random(n) < 0.05, e == 3]), 1.5, 0.1)
-    nrm = nrm + rng.normal(0, 1, nrm.shape) * tilt[:, None]
-    nrm /= np.linalg.norm(nrm, axis=1, keepdims=True)
-    R, t = Twc[:3, :3].astype(np.float64), Twc[:3, 3].astype(np.float64)
-    Xw = X @ R.T + t
-    nw = nrm @ R.T
-    m = len(Xw)
-    dsc = np.vstack([desc, rng.integers(0, 256, (extra, 32), dtype=np.uint8)])
-    return dict(pos=Xw.astype(np.float32), desc=dsc, obs=rng.integers(0, 5, m).astype(np.int32),
-                max_dist=mx.astype(np.float32), min_dist=mn.astype(np.float32), normal=nw.astype(np.float32),
-                skip=(rng.random(m) < 0.08).astype(np.uint8))
 
 
 def cur_frame(rng, k1, d1, scale, Rs, stereo=True):

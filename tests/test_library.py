@@ -38,6 +38,7 @@ def test_invalid_arguments_rejected_without_device():
     assert L.ORBextractor_destroy(None) == ORB_E_INVALID
     assert L.ORBmatcher_destroy(None) == ORB_E_INVALID
     assert L.ORBmatcher_create(0.6, 1, None) == ORB_E_INVALID
+    assert L.ORBmatcher_last_search_plan(None, ptr(np.zeros(6, np.int32))) == ORB_E_INVALID
 
 
 def test_descriptor_distance_host_entry():
