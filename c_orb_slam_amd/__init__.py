@@ -14,3 +14,4 @@ __all__ = ["ORBextractor", "ORBmatcher", "Frame", "MapPoints", "KP_DTYPE", "OrbG
 from .ransac import Initializer, PnPsolver, Rng, Sim3Solver  # noqa: F401
 from .vocabulary import BowVector, ORBVocabulary  # noqa: F401
 from .keyframe_database import KeyFrameDatabase  # noqa: F401
+from .map import Map  # noqa: F401

@@ -281,6 +281,24 @@ def lib():
     L.KeyFrameDatabase_enable_timing.argtypes = [vp, i32]
     L.KeyFrameDatabase_last_timings.argtypes = [vp, vp]
     L.orbgpu_unit_set_kfdb_initial_capacity.argtypes = [i32, i32]
+    L.Map_create.argtypes = [P(vp)]
+    L.Map_destroy.argtypes = [vp]
+    L.Map_clear.argtypes = [vp]
+    L.Map_size.argtypes = [vp, P(i32), P(C.c_longlong), P(C.c_longlong)]
+    L.Map_AddKeyFrame.argtypes = [vp, C.c_int32, i32, vp, vp]
+    L.Map_SetMapPointMatches.argtypes = [vp, C.c_int32, i32, vp, vp, vp]
+    L.Map_EraseMapPoint.argtypes = [vp, C.c_int32]
+    L.Map_ReplaceMapPoint.argtypes = [vp, C.c_int32, C.c_int32]
+    L.Map_EraseKeyFrame.argtypes = [vp, C.c_int32]
+    L.Map_SetNeighbours.argtypes = [vp, C.c_int32, i32, vp, C.c_int32, i32, vp]
+    L.KeyFrame_UpdateConnections.argtypes = [vp, C.c_int32, vp]
+    L.KeyFrame_UpdateConnections_batch.argtypes = [vp, i32, vp, vp]
+    L.Tracking_UpdateLocalMap_batch.argtypes = [vp, vp, i32, vp]
+    L.Map_enable_timing.argtypes = [vp, i32]
+    L.Map_last_timings.argtypes = [vp, vp]
+    L.orbgpu_unit_set_map_initial_capacity.argtypes = [i32, i32, i32]
+    L.orbgpu_unit_set_map_chunk.argtypes = [i32]
+    L.orbgpu_unit_set_map_lds_slots.argtypes = [i32]
     L.Initializer_create.argtypes = [vp, i32, vp, f32, i32, P(vp)]
     L.Initializer_destroy.argtypes = [vp]
     L.Initializer_Initialize.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp, vp, P(i32), vp]
@@ -361,6 +379,20 @@ class orb_kfdb_result(C.Structure):
                 ("scored_id", C.c_void_p), ("scored_words", C.c_void_p), ("scored_score", C.c_void_p),
                 ("scored_acc", C.c_void_p), ("n_scored", C.c_int), ("n_sharing", C.c_int),
                 ("maxCommonWords", C.c_int), ("minCommonWords", C.c_int), ("bestAccScore", C.c_float)]
+
+
+class orb_connections(C.Structure):
+    _fields_ = [("cap_counter", C.c_int), ("counter_id", C.c_void_p), ("counter_n", C.c_void_p),
+                ("cap_ordered", C.c_int), ("ordered_id", C.c_void_p), ("ordered_w", C.c_void_p),
+                ("n_counter", C.c_int), ("n_ordered", C.c_int)]
+
+
+class orb_localupdate(C.Structure):
+    _fields_ = [("N", C.c_int), ("cur_mp", C.c_void_p), ("table", C.POINTER(orb_localmap)), ("kf_cap", C.c_int),
+                ("pt_cap", C.c_int), ("local_kf", C.c_void_p), ("local_mp", C.c_void_p), ("cur_row", C.c_void_p),
+                ("row", C.c_void_p), ("pos", C.c_void_p), ("desc", C.c_void_p), ("observations", C.c_void_p),
+                ("max_dist", C.c_void_p), ("min_dist", C.c_void_p), ("normal", C.c_void_p), ("skip", C.c_void_p),
+                ("n_kf", C.c_int32), ("ref_kf", C.c_int32), ("n_pt", C.c_int32), ("reserved", C.c_int32)]
 
 
 class pose_frame(C.Structure):

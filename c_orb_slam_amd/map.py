@@ -1,0 +1,116 @@
+"""Host-side mirror of the part of the reference's Map / KeyFrame / MapPoint that relates keyframes
+to map points (include/Map.h, src/KeyFrame.cc, src/MapPoint.cc): the rows live in device memory,
+mutations go through the C ABI into a host mirror, and the two counting functions over the
+relation -- KeyFrame::UpdateConnections here, Tracking::UpdateLocalMap as
+ORBmatcher.UpdateLocalMap -- run in the HIP library.
+
+Two rules hold everywhere: the vote reads only the slots whose observation exists (`observed`),
+UpdateLocalPoints reads every slot; and ascending keyframe id stands in for the address order of
+the reference's pointer-keyed std::map / std::set."""
+import ctypes as C
+
+import numpy as np
+
+from ._lib import ORB_E_CAPACITY, OrbGpuError, check, lib, orb_connections, ptr
+
+
+class Map:
+    def __init__(self):
+        self._L = lib()
+        h = C.c_void_p()
+        check(self._L.Map_create(C.byref(h)), "Map_create")
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.Map_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+    def clear(self):
+        check(self._L.Map_clear(self._h), "Map_clear")
+
+    def size(self):
+        """(live keyframes, slots of their rows, observed slots among them)"""
+        n, s, o = C.c_int(), C.c_longlong(), C.c_longlong()
+        check(self._L.Map_size(self._h, C.byref(n), C.byref(s), C.byref(o)), "Map_size")
+        return n.value, s.value, o.value
+
+    def AddKeyFrame(self, id, mp, observed=None):
+        """Map::AddKeyFrame with the keyframe's mvpMapPoints (ids, -1 = none); observed[slot] = the
+        point's mObservations holds (keyframe, slot) (None: all)."""
+        mp = np.ascontiguousarray(mp, np.int32)
+        ob = None if observed is None else np.ascontiguousarray(observed, np.uint8)
+        check(self._L.Map_AddKeyFrame(self._h, int(id), len(mp), ptr(mp) if len(mp) else None,
+                                      ptr(ob) if ob is not None and len(ob) else None), "Map_AddKeyFrame")
+
+    def SetMapPointMatches(self, id, slots, mp, observed=None):
+        """KeyFrame::AddMapPoint / EraseMapPointMatch / ReplaceMapPointMatch and MapPoint::AddObservation /
+        EraseObservation: slot slots[k] of keyframe `id` takes mp[k] (-1 empties it) with observed[k]."""
+        sl = np.ascontiguousarray(slots, np.int32)
+        mp = np.ascontiguousarray(mp, np.int32)
+        ob = None if observed is None else np.ascontiguousarray(observed, np.uint8)
+        check(self._L.Map_SetMapPointMatches(self._h, int(id), len(sl), ptr(sl) if len(sl) else None,
+                                             ptr(mp) if len(sl) else None,
+                                             ptr(ob) if ob is not None and len(ob) else None),
+              "Map_SetMapPointMatches")
+
+    def EraseMapPoint(self, mp):
+        """MapPoint::SetBadFlag"""
+        check(self._L.Map_EraseMapPoint(self._h, int(mp)), "Map_EraseMapPoint")
+
+    def ReplaceMapPoint(self, mp, by):
+        """MapPoint::Replace"""
+        check(self._L.Map_ReplaceMapPoint(self._h, int(mp), int(by)), "Map_ReplaceMapPoint")
+
+    def EraseKeyFrame(self, id):
+        """KeyFrame::SetBadFlag"""
+        check(self._L.Map_EraseKeyFrame(self._h, int(id)), "Map_EraseKeyFrame")
+
+    def SetNeighbours(self, id, best10, parent=-1, children=()):
+        """GetBestCovisibilityKeyFrames(10), GetParent and GetChilds of keyframe `id` as ids."""
+        b = np.ascontiguousarray(best10, np.int32)
+        c = np.ascontiguousarray(children, np.int32)
+        check(self._L.Map_SetNeighbours(self._h, int(id), len(b), ptr(b) if len(b) else None, int(parent), len(c),
+                                        ptr(c) if len(c) else None), "Map_SetNeighbours")
+
+    def UpdateConnections_batch(self, ids, cap_counter=256, cap_ordered=64):
+        """KeyFrame::UpdateConnections of every keyframe of `ids` against one map state.  -> per
+        keyframe (counter_id, counter_n, ordered_id, ordered_w): KFcounter in ascending id, and
+        mvpOrderedConnectedKeyFrames / mvOrderedWeights.  On ORB_E_CAPACITY the call is repeated
+        once with the counts it reported."""
+        ids = np.ascontiguousarray(ids, np.int32)
+        n = len(ids)
+        caps = [(int(cap_counter), int(cap_ordered))] * n
+        for attempt in range(2):
+            bufs = [tuple(np.zeros(max(c, 1), np.int32) for c in (cc, cc, co, co)) for cc, co in caps]
+            ra = (orb_connections * max(n, 1))()
+            for i in range(n):
+                r, b = ra[i], bufs[i]
+                r.cap_counter, r.cap_ordered = caps[i]
+                r.counter_id, r.counter_n, r.ordered_id, r.ordered_w = (ptr(x) for x in b)
+            rc = self._L.KeyFrame_UpdateConnections_batch(self._h, n, ptr(ids) if n else None, ra)
+            if rc == ORB_E_CAPACITY and attempt == 0:
+                caps = [(max(ra[i].n_counter, 1), max(ra[i].n_ordered, 1)) for i in range(n)]
+                continue
+            check(rc, "KeyFrame_UpdateConnections_batch")
+            break
+        return [(b[0][:ra[i].n_counter].copy(), b[1][:ra[i].n_counter].copy(), b[2][:ra[i].n_ordered].copy(),
+                 b[3][:ra[i].n_ordered].copy()) for i, b in enumerate(bufs)]
+
+    def UpdateConnections(self, id, **kw):
+        return self.UpdateConnections_batch([id], **kw)[0]
+
+    def enable_timing(self, on=True):
+        check(self._L.Map_enable_timing(self._h, int(on)), "Map_enable_timing")
+
+    def last_timings(self):
+        """ms of the last timed UpdateLocalMap: (index rebuild or -1, vote, keyframe selection, local
+        points, remap + gather), HIP events."""
+        ms = np.zeros(5, np.float32)
+        check(self._L.Map_last_timings(self._h, ptr(ms)), "Map_last_timings")
+        return ms
+
+
+__all__ = ["Map", "OrbGpuError"]

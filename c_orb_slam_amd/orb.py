@@ -532,6 +532,48 @@ class ORBmatcher:
         del keep
         return nm[:len(frames)], nv[:len(frames)]
 
+    def UpdateLocalMap(self, map, cur_mps, bad=None, kf_cap=128, pt_cap=8192, retry=True):
+        """Tracking::UpdateLocalMap (Tracking.cc:1195-1339) per frame over the device-resident `map`
+        (c_orb_slam_amd.Map), host arrays (Tracking_UpdateLocalMap_batch): cur_mps[f] (int32 numpy,
+        mCurrentFrame.mvpMapPoints as global map-point ids) has its bad points cleared in place; bad
+        (uint8, one flag per row of the map-point table) = isBad().  -> per frame a dict with local_kf,
+        ref_kf, local_mp (global ids, mvpLocalMapPoints order), cur_row (the local row of every
+        keypoint's point, or -1), n_kf, n_pt; an empty vote gives n_kf = 0 and cur_row None.  On
+        ORB_E_CAPACITY the call is repeated once with the counts it reported (retry=False raises)."""
+        from ._lib import orb_localmap, orb_localupdate
+        n = len(cur_mps)
+        for c in cur_mps:
+            assert c.dtype == np.int32 and c.flags.c_contiguous
+        table = None
+        if bad is not None:
+            bad = np.ascontiguousarray(bad, np.uint8)
+            table = orb_localmap(len(bad), None, None, None, None, None, None, ptr(bad) if len(bad) else None)
+        caps = [(int(kf_cap), int(pt_cap))] * n
+        check(self._L.ORBmatcher_set_device_pointers(self._h, 0))
+        for attempt in range(2):
+            bufs = [dict(local_kf=np.full(max(k, 1), -1, np.int32), local_mp=np.full(max(p, 1), -1, np.int32),
+                         cur_row=np.full(max(len(c), 1), -1, np.int32)) for (k, p), c in zip(caps, cur_mps)]
+            ua = (orb_localupdate * max(n, 1))()
+            for f in range(n):
+                u, b = ua[f], bufs[f]
+                u.N, u.cur_mp = len(cur_mps[f]), (ptr(cur_mps[f]) if len(cur_mps[f]) else None)
+                u.table = C.pointer(table) if table is not None else None
+                u.kf_cap, u.pt_cap = caps[f]
+                u.local_kf, u.local_mp, u.cur_row = ptr(b["local_kf"]), ptr(b["local_mp"]), ptr(b["cur_row"])
+            rc = self._L.Tracking_UpdateLocalMap_batch(self._h, map._h, n, ua)
+            if rc == ORB_E_CAPACITY and attempt == 0 and retry:
+                caps = [(max(ua[f].n_kf, caps[f][0]), max(ua[f].n_pt, caps[f][1])) for f in range(n)]
+                continue
+            check(rc, "Tracking_UpdateLocalMap_batch")
+            break
+        out = []
+        for f in range(n):
+            u, b = ua[f], bufs[f]
+            out.append(dict(n_kf=u.n_kf, ref_kf=u.ref_kf, n_pt=u.n_pt, local_kf=b["local_kf"][:u.n_kf].copy(),
+                            local_mp=b["local_mp"][:u.n_pt].copy(),
+                            cur_row=b["cur_row"][:len(cur_mps[f])].copy() if u.n_kf > 0 else None))
+        return out
+
     def UnprojectStereo_device(self, frames):
         """Frame::UnprojectStereo (Frame.cc:666-680) for every keypoint of device-resident frames,
         enqueued on this matcher's stream (ORBmatcher_stream): frames[f] is a dict of torch device

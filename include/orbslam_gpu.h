@@ -576,6 +576,140 @@ int KeyFrameDatabase_DetectRelocalizationCandidates_batch(KeyFrameDatabase_h h, 
 int KeyFrameDatabase_enable_timing(KeyFrameDatabase_h h, int on);
 int KeyFrameDatabase_last_timings(KeyFrameDatabase_h h, float* ms3);
 
+/* ======================================================================
+ * Map: the keyframe <-> map-point observation relation in device memory, and the two counting
+ * functions over it: Tracking::UpdateLocalMap (src/Tracking.cc:1195-1339) and
+ * KeyFrame::UpdateConnections (src/KeyFrame.cc).
+ * Per live keyframe the handle stores one row: mp[slot] = the map-point id of
+ * KeyFrame::mvpMapPoints[slot] (-1 = none) and observed[slot] = whether that point's
+ * mObservations holds (this keyframe, slot).  The two differ for a while in the reference:
+ * Tracking::CreateNewKeyFrame copies the frame's map points into the keyframe at once,
+ * LocalMapping::ProcessNewKeyFrame adds the observations later.
+ *  - The observed rule: the vote (UpdateLocalKeyFrames, UpdateConnections) reads observed slots
+ *    only; UpdateLocalPoints reads every slot.
+ *  - The id-order rule: where the reference iterates a std::map<KeyFrame*, int> or a
+ *    std::set<KeyFrame*> (keyframeCounter, KFcounter, mspChildrens) its order is the keyframes'
+ *    address order; ascending keyframe id stands in for it everywhere here.
+ * Map-point ids are the rows of the caller's map-point table (non-negative int32, as
+ * orb_newpoints.row); keyframe ids are mnId (non-negative, dense: two tables are indexed by them).
+ * Mutations are host calls on host pointers: they update a host mirror, and the next query
+ * uploads the changed rows and rebuilds the inverse index (map point -> observing keyframes) on
+ * the device.  One mutex per handle stands for the map's and the keyframes' mutexes; queries from
+ * several matchers are serialised by it and ordered on the device by an event.
+ * Argument checks come before the device is touched; an otherwise valid call on a NULL handle
+ * answers ORB_E_NODEVICE where no device is visible (ORB_E_INVALID otherwise).
+ * ====================================================================== */
+typedef struct Map_t* Map_h;
+int Map_create(Map_h* out);
+int Map_destroy(Map_h h);
+/* void Map::clear() */
+int Map_clear(Map_h h);
+/* live keyframes, the slots of their rows, and the observed slots among them */
+int Map_size(Map_h h, int* n_keyframes, long long* n_slots, long long* n_observations);
+/* Map::AddKeyFrame with the keyframe's mvpMapPoints (Tracking::CreateNewKeyFrame, KeyFrame's
+ * constructor): N <= 4096 slots, mp[slot] >= 0 or -1, observed[slot] (NULL = all 1).
+ * ORB_E_INVALID: N > 4096, an id already present, a map point held twice in the row. */
+int Map_AddKeyFrame(Map_h h, int32_t id, int N, const int32_t* mp, const uint8_t* observed);
+/* Sparse updates of one row, for KeyFrame::AddMapPoint / EraseMapPointMatch /
+ * ReplaceMapPointMatch and MapPoint::AddObservation / EraseObservation: slot[k] takes mp[k]
+ * (-1 empties it) with observed[k] (NULL = all 1).  ORB_E_INVALID: an unknown id, a slot outside
+ * the row or named twice, a point that the row would then hold twice. */
+int Map_SetMapPointMatches(Map_h h, int32_t id, int count, const int32_t* slot, const int32_t* mp,
+                           const uint8_t* observed);
+/* MapPoint::SetBadFlag (MapPoint.cc): every slot that holds `mp` is emptied. */
+int Map_EraseMapPoint(Map_h h, int32_t mp);
+/* MapPoint::Replace (MapPoint.cc), per keyframe that observes `mp`: the slot takes `by`
+ * (observed), unless `by` is already in that row, in which case the slot is emptied.  A slot that
+ * holds `mp` without the observation is emptied (the reference leaves a bad point there, which
+ * every reader skips). */
+int Map_ReplaceMapPoint(Map_h h, int32_t mp, int32_t by);
+/* KeyFrame::SetBadFlag: erased keyframes are the reference's bad keyframes: they never vote, are
+ * never neighbours, and their storage is reused.  An absent id is ORB_OK. */
+int Map_EraseKeyFrame(Map_h h, int32_t id);
+/* The neighbour record UpdateLocalKeyFrames reads: ids10 = the first n10 <= 10 of
+ * mvpOrderedConnectedKeyFrames (GetBestCovisibilityKeyFrames(10)), parent = mpParent's id or -1,
+ * children = mspChildrens (any order; kept in ascending id order, the id-order rule).  Forwarded
+ * from the places that call KeyFrameDatabase_set_covisibles, and from AddChild / EraseChild /
+ * ChangeParent.  Ids not (or no longer) in the handle are skipped at query time, as bad keyframes
+ * are.  ORB_E_INVALID: `id` is not in the handle. */
+int Map_SetNeighbours(Map_h h, int32_t id, int n10, const int32_t* ids10, int32_t parent, int nchild,
+                      const int32_t* children);
+
+/* void KeyFrame::UpdateConnections() (KeyFrame.cc): the vote over the keyframe's own row (every
+ * slot >= 0; each point's observers counted, the keyframe itself excluded; the observed rule).
+ * counter_* = KFcounter: every keyframe with count > 0 in ascending id (the id-order rule).
+ * ordered_* = mvpOrderedConnectedKeyFrames / mvOrderedWeights: the entries with count >= 15, or
+ * where there is none the single maximum (the first strict maximum in ascending id), sorted by
+ * descending (weight, id): among equal weights the larger id comes first (the reference sorts
+ * pair<int, KeyFrame*> ascending and pushes to the front).  ORB_E_CAPACITY when n_counter >
+ * cap_counter or n_ordered > cap_ordered: the counts needed are set and nothing is written past
+ * a capacity; call again.  AddConnection on the other keyframes, the first-connection parent and
+ * the forwards (Map_SetNeighbours, KeyFrameDatabase_set_covisibles) are the adapter's.
+ * Host pointers; synchronous; runs on the handle's own stream. */
+typedef struct orb_connections {
+    int cap_counter;
+    int32_t* counter_id;         /* out */
+    int32_t* counter_n;          /* out */
+    int cap_ordered;
+    int32_t* ordered_id;         /* out */
+    int32_t* ordered_w;          /* out */
+    int n_counter, n_ordered;    /* out */
+} orb_connections;
+int KeyFrame_UpdateConnections(Map_h h, int32_t id, orb_connections* r);
+/* `count` keyframes against one map state in one launch set (LoopClosing::CorrectLoop) */
+int KeyFrame_UpdateConnections_batch(Map_h h, int count, const int32_t* id, orb_connections* r);
+
+/* void Tracking::UpdateLocalMap()                              Tracking.cc:1195-1339
+ * UpdateLocalKeyFrames (1237-1339): every map point of the frame that is not bad votes for the
+ * keyframes observing it (a point held by two keypoints votes twice; the observed rule); bad
+ * points are cleared from cur_mp.  local_kf = the voted keyframes in ascending id (the id-order
+ * rule), ref_kf = the first strict maximum in that order; then for each voted keyframe in order,
+ * while the list holds at most 80: the first of its best-10 covisibles that is live and not yet
+ * listed, the first such child, and the parent if live and not yet listed -- after which the
+ * whole loop ends (the reference's break sits in the outer loop's body).  An empty vote gives
+ * n_kf = 0, ref_kf = -1, n_pt = 0 and leaves every output array but cur_mp untouched.
+ * UpdateLocalPoints (1214-1235): the rows of local_kf in list order, slots in index order, every
+ * slot >= 0 that is not bad regardless of `observed`, first occurrence kept: local_mp.
+ * Then cur_row[i] = the local row of cur_mp[i] or -1 (what orb_localprep.cur_mp and
+ * ORBmatcher_SearchLocalPoints_batch expect), row[j] = local_mp[j], and with device pointers the
+ * global table's rows gathered into pos / desc / observations / max_dist / min_dist / normal with
+ * skip[j] = 0 (all seven or none; they are the arrays of the frame's orb_localmap).  With device
+ * pointers the rows [n_pt, pt_cap) get row = -1 and skip = 1, so a deferred chain passes
+ * orb_localmap.n = orb_localprep.n = pt_cap without knowing n_pt.
+ * table: the caller's global map-point table; n = its rows, skip = isBad(); pos .. normal are
+ * read by the gather only.  NULL: no point is bad.
+ * Runs on ORBmatcher_stream(h); pointer space per ORBmatcher_set_device_pointers (counts and
+ * this struct stay host).  On a deferred matcher the call joins the chain and n_kf / ref_kf /
+ * n_pt are written when ORBmatcher_finish returns: U must stay in place until then.
+ * Capacity: nothing is written past kf_cap / pt_cap and the counts needed are reported; the
+ * synchronous forms return ORB_E_CAPACITY, a deferred caller compares n_kf > kf_cap and n_pt >
+ * pt_cap after finish and queues the step again with larger arrays.  N <= 4096. */
+typedef struct orb_localupdate {
+    int N;
+    int32_t* cur_mp;             /* in/out (N): mCurrentFrame.mvpMapPoints as global ids */
+    const orb_localmap* table;
+    int kf_cap, pt_cap;
+    int32_t* local_kf;           /* out (kf_cap): mvpLocalKeyFrames as ids */
+    int32_t* local_mp;           /* out (pt_cap): mvpLocalMapPoints as global ids */
+    int32_t* cur_row;            /* out (N) */
+    int32_t* row;                /* out (pt_cap), may be NULL */
+    float* pos;                  /* gather outputs (pt_cap rows), device pointers only */
+    uint8_t* desc;
+    int* observations;
+    float* max_dist;
+    float* min_dist;
+    float* normal;
+    uint8_t* skip;
+    int32_t n_kf, ref_kf, n_pt, reserved;   /* out */
+} orb_localupdate;
+int Tracking_UpdateLocalMap_batch(ORBmatcher_h h, Map_h map, int count, orb_localupdate* U);
+/* Measurement (no reference counterpart): HIP-event times (ms) of the last timed
+ * Tracking_UpdateLocalMap_batch (of its last chunk where the batch ran in several):
+ * ms5 = {index rebuild (-1: nothing had changed), vote, keyframe selection, local points,
+ * remap + gather}.  Waits for that work. */
+int Map_enable_timing(Map_h h, int on);
+int Map_last_timings(Map_h h, float* ms5);
+
 /* DBoW2::FeatureVector (std::map<NodeId, std::vector<unsigned>>) as CSR: strictly ascending
  * node ids, the feature indices of node a at feat[start[a] .. start[a+1]) in insertion order.
  * (Computed by the caller's vocabulary; ORBvoc.txt is not shipped with the reference.) */
@@ -1268,6 +1402,17 @@ int orbgpu_unit_set_ess_dense_max(int rows);
  * pool is compacted when its holes exceed its live entries); 0 restores a default.  Returns 1 on
  * a negative value.  Process-wide, host-side. */
 int orbgpu_unit_set_kfdb_initial_capacity(int slots, int entries);
+/* Test knobs of the Map handle.  Process-wide, host-side; each returns 1 on a value out of range.
+ * initial_capacity: a Map created from now on starts with room for `slots` keyframes, `cells` row
+ * slots and map-point ids below `points` (defaults 1024, 1 << 20, 1 << 16; each doubles when
+ * full); 0 restores a default.  chunk: Tracking_UpdateLocalMap_batch and
+ * KeyFrame_UpdateConnections_batch run at most `frames` queries per launch set (0 = default 64,
+ * less where the first-occurrence scratch would pass 256 MiB).  lds_slots: the vote keeps its
+ * counters in LDS while the handle has at most `slots` keyframe slots (default and maximum 8192;
+ * -1 restores it; 0 sends every vote to counters in device memory). */
+int orbgpu_unit_set_map_initial_capacity(int slots, int cells, int points);
+int orbgpu_unit_set_map_chunk(int frames);
+int orbgpu_unit_set_map_lds_slots(int slots);
 /* Instrumented builds only (make prof): read and clear the BA/pose section timers (32 x u64
  * clock64 deltas of workgroup 0); ORB_E_INVALID in normal builds. */
 int orbgpu_debug_prof(unsigned long long* out32);
