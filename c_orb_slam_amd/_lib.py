@@ -296,6 +296,9 @@ def lib():
     L.Tracking_UpdateLocalMap_batch.argtypes = [vp, vp, i32, vp]
     L.Map_enable_timing.argtypes = [vp, i32]
     L.Map_last_timings.argtypes = [vp, vp]
+    L.Map_SetKeyFrameKeys.argtypes = [vp, C.c_int32, i32, vp, vp, vp, f32]
+    L.LocalMapping_KeyFrameCulling.argtypes = [vp, vp]
+    L.LocalMapping_MapPointCulling.argtypes = [vp, vp]
     L.orbgpu_unit_set_map_initial_capacity.argtypes = [i32, i32, i32]
     L.orbgpu_unit_set_map_chunk.argtypes = [i32]
     L.orbgpu_unit_set_map_lds_slots.argtypes = [i32]
@@ -393,6 +396,19 @@ class orb_localupdate(C.Structure):
                 ("row", C.c_void_p), ("pos", C.c_void_p), ("desc", C.c_void_p), ("observations", C.c_void_p),
                 ("max_dist", C.c_void_p), ("min_dist", C.c_void_p), ("normal", C.c_void_p), ("skip", C.c_void_p),
                 ("n_kf", C.c_int32), ("ref_kf", C.c_int32), ("n_pt", C.c_int32), ("reserved", C.c_int32)]
+
+
+class orb_kfcull(C.Structure):
+    _fields_ = [("n", C.c_int), ("cand", C.c_void_p), ("not_erase", C.c_void_p), ("monocular", C.c_int),
+                ("bad", C.c_void_p), ("nbad", C.c_int), ("cap_bad", C.c_int), ("apply", C.c_int),
+                ("nMPs", C.c_void_p), ("nRedundant", C.c_void_p), ("verdict", C.c_void_p), ("bad_mp", C.c_void_p),
+                ("n_bad", C.c_int)]
+
+
+class orb_pointcull(C.Structure):
+    _fields_ = [("n", C.c_int), ("mp", C.c_void_p), ("first_kf", C.c_void_p), ("found", C.c_void_p),
+                ("visible", C.c_void_p), ("bad", C.c_void_p), ("nbad", C.c_int), ("cur_kf", C.c_int32),
+                ("monocular", C.c_int), ("apply", C.c_int), ("verdict", C.c_void_p), ("observations", C.c_void_p)]
 
 
 class pose_frame(C.Structure):

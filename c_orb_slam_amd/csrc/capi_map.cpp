@@ -340,6 +340,57 @@ int Tracking_UpdateLocalMap_batch(ORBmatcher_h mh, Map_h h, int count, orb_local
     return ORB_OK;
 }
 
+int Map_SetKeyFrameKeys(Map_h h, int32_t id, int N, const uint8_t* octave, const float* uRight, const float* depth,
+                        float thDepth) {
+    if (id < 0 || N < 0 || N > orbgpu::kMapMaxRow || (N > 0 && !octave)) return ORB_E_INVALID;
+    if (!h) return no_handle();
+    std::lock_guard<std::mutex> lk(h->mu);
+    return rc_of(h->map.set_keys(id, N, octave, uRight, depth, thDepth));
+}
+
+int LocalMapping_KeyFrameCulling(Map_h h, orb_kfcull* r) {
+    if (!r || r->n < 0 || r->cap_bad < 0 || r->nbad < 0) return ORB_E_INVALID;
+    if (r->n > 0 && (!r->cand || !r->nMPs || !r->nRedundant || !r->verdict)) return ORB_E_INVALID;
+    if ((r->cap_bad > 0 && !r->bad_mp) || (r->nbad > 0 && !r->bad)) return ORB_E_INVALID;
+    {
+        std::unordered_set<int32_t> seen;   // SetBadFlag runs once per keyframe
+        for (int i = 0; i < r->n; i++)
+            if (!seen.insert(r->cand[i]).second) return ORB_E_INVALID;
+    }
+    if (!h) return no_handle();
+    std::lock_guard<std::mutex> lk(h->mu);
+    orbgpu::MapKfCull c{r->n, r->cand, r->not_erase, r->monocular, r->bad, r->nbad, r->cap_bad,
+                        r->nMPs, r->nRedundant, r->verdict, r->bad_mp, 0};
+    const int e = h->map.cull_keyframes(c);
+    r->n_bad = c.n_bad;
+    if (e) return rc_of(e);
+    if (r->apply) {   // what Map_EraseKeyFrame / Map_EraseMapPoint would do
+        for (int i = 0; i < r->n; i++)
+            if (r->verdict[i] == 1)
+                if (int e2 = h->map.erase_keyframe(r->cand[i])) return rc_of(e2);
+        for (int i = 0; i < r->n_bad; i++)
+            if (int e2 = h->map.erase_point(r->bad_mp[i])) return rc_of(e2);
+    }
+    return ORB_OK;
+}
+
+int LocalMapping_MapPointCulling(Map_h h, orb_pointcull* r) {
+    if (!r || r->n < 0 || r->nbad < 0 || (r->nbad > 0 && !r->bad)) return ORB_E_INVALID;
+    if (r->n > 0 && (!r->mp || !r->first_kf || !r->found || !r->visible || !r->verdict)) return ORB_E_INVALID;
+    for (int i = 0; i < r->n; i++)
+        if (r->mp[i] < 0 || r->visible[i] <= 0) return ORB_E_INVALID;
+    if (!h) return no_handle();
+    std::lock_guard<std::mutex> lk(h->mu);
+    orbgpu::MapPtCull c{r->n, r->mp, r->first_kf, r->found, r->visible, r->bad, r->nbad, r->cur_kf, r->monocular,
+                        r->verdict, r->observations};
+    if (int e = h->map.cull_points(c)) return rc_of(e);
+    if (r->apply)
+        for (int i = 0; i < r->n; i++)
+            if (r->verdict[i] == 2 || r->verdict[i] == 3)
+                if (int e2 = h->map.erase_point(r->mp[i])) return rc_of(e2);
+    return ORB_OK;
+}
+
 int Map_enable_timing(Map_h h, int on) {
     if (!h) return no_handle();
     std::lock_guard<std::mutex> lk(h->mu);

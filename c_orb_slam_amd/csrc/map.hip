@@ -386,6 +386,177 @@ __global__ void __launch_bounds__(MT) k_map_fill(int32_t* __restrict__ a, size_t
     for (size_t i = (size_t)blockIdx.x * MT + threadIdx.x; i < n; i += (size_t)gridDim.x * MT) a[i] = v;
 }
 
+// ---------------------------------------------------------------- culling
+// LocalMapping::KeyFrameCulling (LocalMapping.cc) and MapPointCulling over the handle.
+//   k_cull_index   the observing cells of every point (slot * 4096 + index) in the places of
+//                  pt_start, and nObs; same predicate as k_map_csr_count, so the ranges agree
+//   k_cull_count   one workgroup per candidate: nMPs / nRedundant against the initial state
+//   k_cull_walk    one workgroup walks the candidates in order; from the first cull on it counts
+//                  each later candidate again against dead[] and scr[], and on a cull takes the
+//                  row's observations off nObs and compacts the points that went bad in slot order
+//   k_cull_points  MapPointCulling, one point per thread
+
+constexpr int kCullBad = 1 << 30;   // scr: the point went bad in this call
+
+struct CullDev {
+    const MapSlotDev* slots;
+    const int32_t* mp;
+    const uint8_t* obs;
+    const uint8_t* oct;
+    const uint8_t* flags;
+    const int32_t* pt_start;
+    const uint32_t* pt_obs;
+    const int32_t* nobs;
+    int32_t* scr;            // written and read again inside k_cull_walk
+    uint8_t* dead;           // the same
+    const uint8_t* bad;
+    int32_t nbad, monocular;
+};
+
+__global__ void __launch_bounds__(MT)
+k_cull_index(const MapSlotDev* __restrict__ slots, const int32_t* __restrict__ order,
+             const int32_t* __restrict__ mp, const uint8_t* __restrict__ obs, const uint8_t* __restrict__ flags,
+             int npts, int32_t* __restrict__ cursor, uint32_t* __restrict__ pt_obs, int32_t* __restrict__ nobs) {
+    const int slot = order[blockIdx.x];
+    const MapSlotDev S = slots[slot];
+    for (int i = threadIdx.x; i < S.n; i += MT) {
+        const int p = mp[S.off + i];
+        if (p >= 0 && p < npts && obs[S.off + i]) {
+            pt_obs[atomicAdd(&cursor[p], 1)] = (uint32_t)slot * kMapMaxRow + (uint32_t)i;
+            atomicAdd(&nobs[p], (flags[S.off + i] & kMapKeyStereo) ? 2 : 1);
+        }
+    }
+}
+
+// slot i of the candidate's row S (keyframe slot `slot`): LocalMapping.cc KeyFrameCulling's loop body
+__device__ __forceinline__ void cull_count_cell(const CullDev& C, int slot, const MapSlotDev& S, int i, int& nmps,
+                                                int& nred) {
+    const int cell = S.off + i;
+    const int p = C.mp[cell];
+    if (p < 0) return;
+    if (C.bad && p < C.nbad && C.bad[p]) return;
+    const int sc = C.scr[p];
+    if (sc & kCullBad) return;
+    if (!C.monocular && (C.flags[cell] & kMapKeyFar)) return;
+    nmps++;
+    if (C.nobs[p] - sc <= 3) return;   // pMP->Observations() > thObs
+    const int level = C.oct[cell];
+    const int hi = C.pt_start[p + 1];
+    int n = 0;
+    for (int k = C.pt_start[p]; k < hi && n < 3; k++) {
+        const uint32_t code = C.pt_obs[k];
+        const int s2 = (int)(code / kMapMaxRow);
+        if (s2 == slot || C.dead[s2]) continue;
+        if ((int)C.oct[C.slots[s2].off + (int)(code % kMapMaxRow)] <= level + 1) n++;
+    }
+    nred += n >= 3;
+}
+
+__global__ void __launch_bounds__(MT)
+k_cull_count(CullDev C, const int32_t* __restrict__ cand_slot, int32_t* __restrict__ nmps, int32_t* __restrict__ nred) {
+    __shared__ int s_w[MT / 64];
+    const int slot = cand_slot[blockIdx.x];
+    int a = 0, b = 0;
+    if (slot >= 0) {
+        const MapSlotDev S = C.slots[slot];
+        for (int i = threadIdx.x; i < S.n; i += MT) cull_count_cell(C, slot, S, i, a, b);
+    }
+    int ta, tb;
+    (void)block_excl_scan<MT>(a, s_w, &ta);
+    (void)block_excl_scan<MT>(b, s_w, &tb);
+    if (threadIdx.x == 0) {
+        nmps[blockIdx.x] = ta;
+        nred[blockIdx.x] = tb;
+    }
+}
+
+// nmps / nred hold k_cull_count's answers on entry
+__global__ void __launch_bounds__(MT)
+k_cull_walk(CullDev C, int n, const int32_t* __restrict__ cand_slot, const uint8_t* __restrict__ not_erase,
+            int cap_bad, int32_t* nmps, int32_t* nred, int32_t* __restrict__ verdict, int32_t* __restrict__ bad_mp,
+            int32_t* __restrict__ n_bad) {
+    __shared__ int s_w[MT / 64];
+    int nout = 0;
+    bool culled = false;
+    for (int c = 0; c < n; c++) {   // everything that steers the loop is block-uniform
+        const int slot = cand_slot[c];
+        if (slot < 0) {
+            if (threadIdx.x == 0) {
+                verdict[c] = 3;
+                nmps[c] = 0;
+                nred[c] = 0;
+            }
+            continue;
+        }
+        const MapSlotDev S = C.slots[slot];
+        int ta, tb;
+        if (!culled) {
+            ta = nmps[c];
+            tb = nred[c];
+        } else {
+            int a = 0, b = 0;
+            for (int i = threadIdx.x; i < S.n; i += MT) cull_count_cell(C, slot, S, i, a, b);
+            (void)block_excl_scan<MT>(a, s_w, &ta);
+            (void)block_excl_scan<MT>(b, s_w, &tb);
+            if (threadIdx.x == 0) {
+                nmps[c] = ta;
+                nred[c] = tb;
+            }
+        }
+        int v = 0;
+        if ((double)tb > 0.9 * (double)ta) v = (not_erase && not_erase[c]) ? 2 : 1;
+        if (threadIdx.x == 0) verdict[c] = v;
+        if (v != 1) continue;
+        // KeyFrame::SetBadFlag: EraseObservation(this) of every slot, in slot order
+        culled = true;
+        if (threadIdx.x == 0) C.dead[slot] = 1;
+        for (int i0 = 0; i0 < S.n; i0 += MT) {
+            const int i = i0 + (int)threadIdx.x;
+            int p = -1;
+            bool newly = false;
+            if (i < S.n && C.obs[S.off + i]) {
+                p = C.mp[S.off + i];
+                if (p >= 0) {   // a row holds a point once: no two lanes share p
+                    int sc = C.scr[p];
+                    if (!(sc & kCullBad)) {
+                        sc += (C.flags[S.off + i] & kMapKeyStereo) ? 2 : 1;
+                        if (C.nobs[p] - sc <= 2) {   // MapPoint::EraseObservation: nObs <= 2 -> SetBadFlag
+                            sc |= kCullBad;
+                            newly = true;
+                        }
+                        C.scr[p] = sc;
+                    }
+                }
+            }
+            int total;
+            const int r = nout + block_excl_scan<MT>(newly, s_w, &total);
+            if (newly && r < cap_bad) bad_mp[r] = p;
+            nout += total;
+        }
+        __syncthreads();   // scr and dead of this cull before the next candidate's count
+    }
+    if (threadIdx.x == 0) *n_bad = nout;
+}
+
+__global__ void __launch_bounds__(MT)
+k_cull_points(int n, const int32_t* __restrict__ mp, const int32_t* __restrict__ first_kf,
+              const int32_t* __restrict__ found, const int32_t* __restrict__ visible, const uint8_t* __restrict__ bad,
+              int nbad, const int32_t* __restrict__ nobs, int npts, int cur_kf, int th_obs,
+              int32_t* __restrict__ verdict, int32_t* __restrict__ observations) {
+    const int t = blockIdx.x * MT + threadIdx.x;
+    if (t >= n) return;
+    const int p = mp[t];
+    const int no = p < npts ? nobs[p] : 0;   // never observed
+    const int age = cur_kf - first_kf[t];
+    int v = 0;
+    if (bad && p < nbad && bad[p]) v = 1;
+    else if ((float)found[t] / (float)visible[t] < 0.25f) v = 2;   // MapPoint::GetFoundRatio
+    else if (age >= 2 && no <= th_obs) v = 3;
+    else if (age >= 3) v = 4;
+    verdict[t] = v;
+    observations[t] = no;
+}
+
 template <class T>
 int regrow(T** p, size_t count) {
     if (*p) (void)hipFree(*p);
@@ -402,7 +573,8 @@ Map::~Map() {
         if (e) (void)hipEventDestroy(e);
     if (ev_done_) (void)hipEventDestroy(ev_done_);
     void* bufs[] = {d_slots_, d_nb_, d_order_, d_child_, d_id2slot_, d_mp_, d_obs_, d_pt_list_, d_pt_start_,
-                    d_pt_cursor_, d_work_, d_scr_, d_counts_, d_q_};
+                    d_pt_cursor_, d_work_, d_scr_, d_counts_, d_q_, d_oct_, d_flags_, d_pt_obs_, d_nobs_,
+                    d_cull_scr_, d_dead_, d_cull_io_};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     if (s_) (void)hipStreamDestroy(s_);
@@ -427,6 +599,8 @@ int Map::init(int slots, int cells, int points) {
     if (int e = regrow(&d_pt_cursor_, (size_t)pt_cap_ + 1)) return e;
     h_mp_.assign((size_t)pool_cap_, -1);
     h_obs_.assign((size_t)pool_cap_, 0);
+    h_oct_.assign((size_t)pool_cap_, 0);
+    h_flags_.assign((size_t)pool_cap_, 0);
     return 0;
 }
 
@@ -478,18 +652,22 @@ void Map::set_cell(int slot, int idx, int32_t mp, uint8_t obs) {
 int Map::repack(long long new_cap) {
     if (new_cap > 0x7fffffffLL) return -3;
     std::vector<int32_t> nm((size_t)new_cap, -1);
-    std::vector<uint8_t> no((size_t)new_cap, 0);
+    std::vector<uint8_t> no((size_t)new_cap, 0), nk((size_t)new_cap, 0), nf((size_t)new_cap, 0);
     long long used = 0;
     for (size_t sl = 0; sl < slots_.size(); sl++) {
         MapSlotDev& S = slots_[sl];
         if (!S.live) continue;
         std::memcpy(nm.data() + used, h_mp_.data() + S.off, 4 * (size_t)S.n);
         std::memcpy(no.data() + used, h_obs_.data() + S.off, (size_t)S.n);
+        std::memcpy(nk.data() + used, h_oct_.data() + S.off, (size_t)S.n);
+        std::memcpy(nf.data() + used, h_flags_.data() + S.off, (size_t)S.n);
         S.off = (int32_t)used;
         used += S.n;
     }
     h_mp_.swap(nm);
     h_obs_.swap(no);
+    h_oct_.swap(nk);
+    h_flags_.swap(nf);
     pool_cap_ = new_cap;
     pool_used_ = used;
     all_rows_dirty_ = meta_dirty_ = index_dirty_ = true;
@@ -520,6 +698,8 @@ int Map::add_keyframe(int32_t id, int N, const int32_t* mp, const uint8_t* obser
     for (int i = 0; i < N; i++) {   // the span may hold an erased row's cells
         h_mp_[(size_t)pool_used_ + i] = -1;
         h_obs_[(size_t)pool_used_ + i] = 0;
+        h_oct_[(size_t)pool_used_ + i] = 0;   // keys never set: octave 0, monocular, not far
+        h_flags_[(size_t)pool_used_ + i] = 0;
     }
     pool_used_ += N;
     live_cells_ += N;
@@ -595,6 +775,21 @@ int Map::set_neighbours(int32_t id, int n10, const int32_t* ids10, int32_t paren
     return 0;
 }
 
+int Map::set_keys(int32_t id, int N, const uint8_t* octave, const float* uRight, const float* depth, float thDepth) {
+    const int sl = slot_of(id);
+    if (sl < 0 || N != slots_[sl].n) return -1;
+    const size_t off = (size_t)slots_[sl].off;
+    for (int i = 0; i < N; i++) {
+        h_oct_[off + i] = octave[i];
+        uint8_t f = 0;
+        if (uRight && uRight[i] >= 0.f) f |= kMapKeyStereo;
+        if (depth && (depth[i] > thDepth || depth[i] < 0.f)) f |= kMapKeyFar;
+        h_flags_[off + i] = f;
+    }
+    cull_dirty_ = true;
+    return 0;
+}
+
 int Map::clear() {
     slots_.clear();
     nb_.clear();
@@ -634,6 +829,7 @@ int Map::leave(hipStream_t s) {
 int Map::sync_device(hipStream_t s) {
     timed_rebuild_ = false;
     if (!all_rows_dirty_ && !meta_dirty_ && !index_dirty_ && dirty_rows_.empty()) return 0;
+    cull_dirty_ = true;   // the cell index and nObs follow at the next culling call
     const int nslots = (int)slots_.size();
     // growth: nothing queued may still read the old buffers
     if (nslots > slot_cap_ || pool_cap_ > dev_pool_cap_ || npts_ > pt_cap_ || nid_ > id_cap_) {
@@ -882,6 +1078,159 @@ int Map::timings(float* ms5) {
     if (timed_rebuild_) ORB_HIP_CHECK(hipEventElapsedTime(&ms5[0], ev_[0], ev_[1]));
     for (int i = 0; i < 4; i++) ORB_HIP_CHECK(hipEventElapsedTime(&ms5[1 + i], ev_[2 + i], ev_[3 + i]));
     return 0;
+}
+
+// ---------------------------------------------------------------- culling
+
+// After sync_device: the key attributes, the cell index and nObs, when a mutation or
+// Map_SetKeyFrameKeys came since the last culling call.  UpdateLocalMap and UpdateConnections
+// never pay for them.
+int Map::sync_cull(hipStream_t s) {
+    const int nslots = (int)slots_.size();
+    if (dev_pool_cap_ > cull_pool_cap_ || pt_cap_ > cull_pt_cap_ || slot_cap_ > cull_slot_cap_) {
+        if (int e = drain()) return e;
+        ORB_HIP_CHECK(hipStreamSynchronize(s));
+    }
+    if (dev_pool_cap_ > cull_pool_cap_) {
+        if (int e = regrow(&d_oct_, (size_t)dev_pool_cap_)) return e;
+        if (int e = regrow(&d_flags_, (size_t)dev_pool_cap_)) return e;
+        if (int e = regrow(&d_pt_obs_, (size_t)dev_pool_cap_)) return e;
+        cull_pool_cap_ = dev_pool_cap_;
+        cull_dirty_ = true;
+    }
+    if (pt_cap_ > cull_pt_cap_) {
+        if (int e = regrow(&d_nobs_, (size_t)pt_cap_ + 1)) return e;
+        if (int e = regrow(&d_cull_scr_, (size_t)pt_cap_ + 1)) return e;
+        cull_pt_cap_ = pt_cap_;
+        cull_dirty_ = true;
+    }
+    if (slot_cap_ > cull_slot_cap_) {
+        if (int e = regrow(&d_dead_, (size_t)slot_cap_)) return e;
+        cull_slot_cap_ = slot_cap_;
+    }
+    if (!cull_dirty_) return 0;
+    if (pool_used_ > 0) {
+        ORB_HIP_CHECK(hipMemcpyAsync(d_oct_, h_oct_.data(), (size_t)pool_used_, hipMemcpyHostToDevice, s));
+        ORB_HIP_CHECK(hipMemcpyAsync(d_flags_, h_flags_.data(), (size_t)pool_used_, hipMemcpyHostToDevice, s));
+    }
+    ORB_HIP_CHECK(hipMemsetAsync(d_nobs_, 0, 4 * ((size_t)npts_ + 1), s));
+    if (n_live_dev_ > 0 && npts_ > 0 && nslots > 0) {
+        ORB_HIP_CHECK(hipMemcpyAsync(d_pt_cursor_, d_pt_start_, 4 * ((size_t)npts_ + 1), hipMemcpyDeviceToDevice, s));
+        hipLaunchKernelGGL(k_cull_index, dim3(n_live_dev_), dim3(MT), 0, s, d_slots_, d_order_, d_mp_, d_obs_, d_flags_,
+                           (int)npts_, d_pt_cursor_, d_pt_obs_, d_nobs_);
+        ORB_HIP_CHECK(hipGetLastError());
+    }
+    ORB_HIP_CHECK(hipStreamSynchronize(s));   // the mirror is pageable
+    cull_dirty_ = false;
+    return 0;
+}
+
+namespace {
+size_t al256(size_t n) { return (n + 255) & ~(size_t)255; }
+}  // namespace
+
+int Map::cull_keyframes(MapKfCull& c) {
+    hipStream_t s = s_;
+    const int n = c.n;
+    c.n_bad = 0;
+    if (n == 0) return 0;
+    std::vector<int32_t> cand_slot((size_t)n);
+    bool any = false;
+    for (int i = 0; i < n; i++) {
+        cand_slot[i] = c.cand[i] == 0 ? -1 : slot_of(c.cand[i]);   // LocalMapping.cc: mnId == 0 is never culled
+        any = any || cand_slot[i] >= 0;
+    }
+    if (!any) {
+        for (int i = 0; i < n; i++) {
+            c.nMPs[i] = c.nRedundant[i] = 0;
+            c.verdict[i] = 3;
+        }
+        return 0;
+    }
+    if (int e = join(s)) return e;
+    if (int e = sync_device(s)) return e;
+    if (int e = sync_cull(s)) return e;
+    const int nslots = (int)slots_.size();
+    const int cap_dev = std::min(c.cap_bad, (int)npts_);   // no more points than there are can go bad
+    // in: cand_slot | not_erase | bad;  out: nmps | nred | verdict | n_bad | bad_mp
+    const size_t o_ne = al256(4 * (size_t)n), o_bad = o_ne + al256((size_t)n);
+    const size_t in_bytes = o_bad + al256((size_t)c.nbad);
+    const size_t o_out = in_bytes, o_nred = o_out + al256(4 * (size_t)n), o_ver = o_nred + al256(4 * (size_t)n);
+    const size_t o_nb = o_ver + al256(4 * (size_t)n), o_bmp = o_nb + 256;
+    const size_t total = o_bmp + al256(4 * (size_t)cap_dev);
+    if (total > cull_io_cap_) {
+        if (int e = drain()) return e;
+        ORB_HIP_CHECK(hipStreamSynchronize(s));
+        if (int e = regrow(&d_cull_io_, total * 2)) return e;
+        cull_io_cap_ = total * 2;
+    }
+    std::vector<uint8_t> io(total, 0);
+    std::memcpy(io.data(), cand_slot.data(), 4 * (size_t)n);
+    if (c.not_erase) std::memcpy(io.data() + o_ne, c.not_erase, (size_t)n);
+    if (c.bad && c.nbad > 0) std::memcpy(io.data() + o_bad, c.bad, (size_t)c.nbad);
+    ORB_HIP_CHECK(hipMemcpyAsync(d_cull_io_, io.data(), in_bytes, hipMemcpyHostToDevice, s));
+    ORB_HIP_CHECK(hipMemsetAsync(d_cull_scr_, 0, 4 * ((size_t)npts_ + 1), s));
+    ORB_HIP_CHECK(hipMemsetAsync(d_dead_, 0, (size_t)std::max(nslots, 1), s));
+    CullDev C;
+    C.slots = d_slots_; C.mp = d_mp_; C.obs = d_obs_; C.oct = d_oct_; C.flags = d_flags_;
+    C.pt_start = d_pt_start_; C.pt_obs = d_pt_obs_; C.nobs = d_nobs_; C.scr = d_cull_scr_; C.dead = d_dead_;
+    C.bad = (c.bad && c.nbad > 0) ? d_cull_io_ + o_bad : nullptr;
+    C.nbad = c.nbad;
+    C.monocular = c.monocular != 0;
+    const int32_t* d_cand = (const int32_t*)d_cull_io_;
+    int32_t* d_nmps = (int32_t*)(d_cull_io_ + o_out);
+    int32_t* d_nred = (int32_t*)(d_cull_io_ + o_nred);
+    int32_t* d_ver = (int32_t*)(d_cull_io_ + o_ver);
+    int32_t* d_nb = (int32_t*)(d_cull_io_ + o_nb);
+    int32_t* d_bmp = (int32_t*)(d_cull_io_ + o_bmp);
+    hipLaunchKernelGGL(k_cull_count, dim3(n), dim3(MT), 0, s, C, d_cand, d_nmps, d_nred);
+    hipLaunchKernelGGL(k_cull_walk, dim3(1), dim3(MT), 0, s, C, n, d_cand,
+                       c.not_erase ? (const uint8_t*)(d_cull_io_ + o_ne) : nullptr, cap_dev, d_nmps, d_nred, d_ver, d_bmp,
+                       d_nb);
+    ORB_HIP_CHECK(hipGetLastError());
+    ORB_HIP_CHECK(hipMemcpyAsync(io.data() + o_out, d_cull_io_ + o_out, total - o_out, hipMemcpyDeviceToHost, s));
+    ORB_HIP_CHECK(hipStreamSynchronize(s));
+    std::memcpy(c.nMPs, io.data() + o_out, 4 * (size_t)n);
+    std::memcpy(c.nRedundant, io.data() + o_nred, 4 * (size_t)n);
+    std::memcpy(c.verdict, io.data() + o_ver, 4 * (size_t)n);
+    std::memcpy(&c.n_bad, io.data() + o_nb, 4);
+    const int nw = std::min(c.n_bad, cap_dev);
+    if (nw > 0) std::memcpy(c.bad_mp, io.data() + o_bmp, 4 * (size_t)nw);
+    if (int e = leave(s)) return e;
+    return c.n_bad > c.cap_bad ? -3 : 0;
+}
+
+int Map::cull_points(const MapPtCull& c) {
+    hipStream_t s = s_;
+    const int n = c.n;
+    if (n == 0) return 0;
+    if (int e = join(s)) return e;
+    if (int e = sync_device(s)) return e;
+    if (int e = sync_cull(s)) return e;
+    // in: mp | first_kf | found | visible | bad;  out: verdict | observations
+    const size_t w = al256(4 * (size_t)n);
+    const size_t o_bad = 4 * w, in_bytes = o_bad + al256((size_t)c.nbad), o_out = in_bytes, total = o_out + 2 * w;
+    if (total > cull_io_cap_) {
+        if (int e = drain()) return e;
+        ORB_HIP_CHECK(hipStreamSynchronize(s));
+        if (int e = regrow(&d_cull_io_, total * 2)) return e;
+        cull_io_cap_ = total * 2;
+    }
+    std::vector<uint8_t> io(total, 0);
+    const int32_t* src[4] = {c.mp, c.first_kf, c.found, c.visible};
+    for (int k = 0; k < 4; k++) std::memcpy(io.data() + k * w, src[k], 4 * (size_t)n);
+    if (c.bad && c.nbad > 0) std::memcpy(io.data() + o_bad, c.bad, (size_t)c.nbad);
+    ORB_HIP_CHECK(hipMemcpyAsync(d_cull_io_, io.data(), in_bytes, hipMemcpyHostToDevice, s));
+    auto at = [&](size_t o) { return (int32_t*)(d_cull_io_ + o); };
+    hipLaunchKernelGGL(k_cull_points, dim3((unsigned)((n + MT - 1) / MT)), dim3(MT), 0, s, n, at(0), at(w), at(2 * w),
+                       at(3 * w), (c.bad && c.nbad > 0) ? (const uint8_t*)(d_cull_io_ + o_bad) : nullptr, c.nbad, d_nobs_,
+                       (int)npts_, (int)c.cur_kf, c.monocular ? 2 : 3, at(o_out), at(o_out + w));
+    ORB_HIP_CHECK(hipGetLastError());
+    ORB_HIP_CHECK(hipMemcpyAsync(io.data() + o_out, d_cull_io_ + o_out, 2 * w, hipMemcpyDeviceToHost, s));
+    ORB_HIP_CHECK(hipStreamSynchronize(s));
+    std::memcpy(c.verdict, io.data() + o_out, 4 * (size_t)n);
+    if (c.observations) std::memcpy(c.observations, io.data() + o_out + w, 4 * (size_t)n);
+    return leave(s);
 }
 
 }  // namespace orbgpu

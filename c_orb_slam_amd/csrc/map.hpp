@@ -27,6 +27,7 @@ constexpr int kMapKfStop = 80;        // Tracking.cc:1290
 constexpr int kMapLdsSlots = 8192;    // vote counters in LDS up to this many keyframe slots (32 KiB)
 constexpr int kMapDefaultChunk = 64;  // frames per launch set of UpdateLocalMap
 constexpr size_t kMapScratchBytes = (size_t)256 << 20;   // first-occurrence scratch of a chunk
+constexpr uint8_t kMapKeyStereo = 1, kMapKeyFar = 2;     // per-cell key flags
 
 struct MapSlotDev {
     int32_t id, off, n, live;   // row = [off, off + n) of the cell pools
@@ -71,6 +72,34 @@ struct MapLocalDev {
     uint8_t* g_skip;
     MapCounts* counts;    // out
 };
+// one LocalMapping::KeyFrameCulling call (host pointers)
+struct MapKfCull {
+    int n;
+    const int32_t* cand;        // keyframe ids in GetVectorCovisibleKeyFrames order
+    const uint8_t* not_erase;   // n or null: KeyFrame::mbNotErase
+    int monocular;
+    const uint8_t* bad;         // the map-point table's isBad() flags, or null
+    int nbad, cap_bad;
+    int32_t* nMPs;              // out n
+    int32_t* nRedundant;        // out n
+    int32_t* verdict;           // out n
+    int32_t* bad_mp;            // out cap_bad
+    int n_bad;                  // out
+};
+// one LocalMapping::MapPointCulling call (host pointers)
+struct MapPtCull {
+    int n;
+    const int32_t* mp;
+    const int32_t* first_kf;
+    const int32_t* found;
+    const int32_t* visible;
+    const uint8_t* bad;
+    int nbad;
+    int32_t cur_kf;
+    int monocular;
+    int32_t* verdict;           // out n
+    int32_t* observations;      // out n or null
+};
 
 class Map {
 public:
@@ -97,6 +126,14 @@ public:
     int set_neighbours(int32_t id, int n10, const int32_t* ids10, int32_t parent, int nchild,
                        const int32_t* children);
     int clear();
+    // The per-slot key attributes of one row: octave, stereo (uRight >= 0) and far (depth > thDepth
+    // or depth < 0).  uRight null: all monocular; depth null: no slot far.  Host mirror only.
+    int set_keys(int32_t id, int N, const uint8_t* octave, const float* uRight, const float* depth, float thDepth);
+
+    // LocalMapping::KeyFrameCulling / MapPointCulling on the handle's stream, synchronous; the
+    // handle itself is not changed (the caller applies the erasures to the mirror).
+    int cull_keyframes(MapKfCull& c);
+    int cull_points(const MapPtCull& c);
 
     // The vote of `count` stored keyframes' own rows (KeyFrame::UpdateConnections), on the
     // handle's stream, synchronous: afterwards votes(q)[slot] is valid until the next call.
@@ -126,6 +163,7 @@ private:
     void mark_row(int slot);
     int repack(long long new_cap);
     int sync_device(hipStream_t s);        // uploads + CSR rebuild
+    int sync_cull(hipStream_t s);          // key attributes + the cell index and nObs, when stale
     int join(hipStream_t s);               // order `s` behind the last query of another stream
     int leave(hipStream_t s);
     int reserve_work(int chunk);
@@ -139,6 +177,8 @@ private:
     std::unordered_map<int32_t, int> slot_of_;
     std::vector<int32_t> h_mp_;
     std::vector<uint8_t> h_obs_;
+    std::vector<uint8_t> h_oct_;     // mvKeysUn[slot].octave, beside h_mp_ / h_obs_
+    std::vector<uint8_t> h_flags_;   // kMapKeyStereo | kMapKeyFar
     std::unordered_map<int32_t, std::vector<uint32_t>> held_;   // map point -> cells (slot * 4096 + idx)
     long long pool_cap_ = 0, pool_used_ = 0, live_cells_ = 0, n_observed_ = 0;
     int32_t npts_ = 0;      // largest map-point id seen + 1
@@ -164,6 +204,19 @@ private:
     int32_t* d_pt_cursor_ = nullptr;   // npts + 1
     int pt_cap_ = 0;
     int n_live_dev_ = 0;
+    // culling: built only when a culling call follows a mutation (sync_cull)
+    bool cull_dirty_ = true;
+    uint8_t* d_oct_ = nullptr;         // cell pools beside d_mp_ / d_obs_
+    uint8_t* d_flags_ = nullptr;
+    uint32_t* d_pt_obs_ = nullptr;     // per point, the observing cells as slot * 4096 + index (CSR over d_pt_start_)
+    long long cull_pool_cap_ = 0;
+    int32_t* d_nobs_ = nullptr;        // per point MapPoint::nObs: 2 per stereo observation, 1 per monocular
+    int32_t* d_cull_scr_ = nullptr;    // per point, zeroed per call: what the call's culls took off nObs | kCullBad
+    int cull_pt_cap_ = 0;
+    uint8_t* d_dead_ = nullptr;        // per keyframe slot, zeroed per call: culled by this call
+    int cull_slot_cap_ = 0;
+    uint8_t* d_cull_io_ = nullptr;     // the arguments and results of one call
+    size_t cull_io_cap_ = 0;
     // work area of a chunk
     int32_t* d_work_ = nullptr;        // cnt | kfslot | rowcnt | rowoff, each chunk x stride
     int32_t* d_scr_ = nullptr;         // chunk x scr_stride, INT_MAX when idle

@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import ORB_E_CAPACITY, OrbGpuError, check, lib, orb_connections, ptr
+from ._lib import ORB_E_CAPACITY, OrbGpuError, check, lib, orb_connections, orb_kfcull, orb_pointcull, ptr
 
 
 class Map:
@@ -101,6 +101,56 @@ class Map:
 
     def UpdateConnections(self, id, **kw):
         return self.UpdateConnections_batch([id], **kw)[0]
+
+    def SetKeyFrameKeys(self, id, octave, uRight=None, depth=None, thDepth=0.0):
+        """The per-slot key attributes of keyframe `id` (the KeyFrame constructor): octave =
+        mvKeysUn[i].octave, uRight = mvuRight (None: monocular), depth = mvDepth with thDepth = mThDepth
+        (None: no slot is far)."""
+        oc = np.ascontiguousarray(octave, np.uint8)
+        ur = None if uRight is None else np.ascontiguousarray(uRight, np.float32)
+        de = None if depth is None else np.ascontiguousarray(depth, np.float32)
+        check(self._L.Map_SetKeyFrameKeys(self._h, int(id), len(oc), ptr(oc) if len(oc) else None,
+                                          ptr(ur) if ur is not None and len(ur) else None,
+                                          ptr(de) if de is not None and len(de) else None, float(thDepth)),
+              "Map_SetKeyFrameKeys")
+
+    def KeyFrameCulling(self, cand, not_erase=None, monocular=False, bad=None, apply=True, cap_bad=64):
+        """LocalMapping::KeyFrameCulling over cand = GetVectorCovisibleKeyFrames() as ids.  -> dict(nMPs,
+        nRedundant, verdict (0 kept, 1 SetBadFlag, 2 mbToBeErased, 3 skipped), bad_mp = the points that went
+        bad through the culls).  apply: the handle erases the culled keyframes and those points.  On
+        ORB_E_CAPACITY the call is repeated once with the count it reported."""
+        cand = np.ascontiguousarray(cand, np.int32)
+        n = len(cand)
+        ne = None if not_erase is None else np.ascontiguousarray(not_erase, np.uint8)
+        b = None if bad is None else np.ascontiguousarray(bad, np.uint8)
+        nmps, nred, ver = (np.zeros(max(n, 1), np.int32) for _ in range(3))
+        cap = int(cap_bad)
+        for attempt in range(2):
+            bmp = np.zeros(max(cap, 1), np.int32)
+            r = orb_kfcull(n, ptr(cand) if n else None, ptr(ne) if ne is not None and n else None, int(monocular),
+                           ptr(b) if b is not None and len(b) else None, 0 if b is None else len(b), cap, int(apply),
+                           ptr(nmps), ptr(nred), ptr(ver), ptr(bmp), 0)
+            rc = self._L.LocalMapping_KeyFrameCulling(self._h, C.byref(r))
+            if rc == ORB_E_CAPACITY and attempt == 0:
+                cap = r.n_bad
+                continue
+            check(rc, "LocalMapping_KeyFrameCulling")
+            break
+        return dict(nMPs=nmps[:n].copy(), nRedundant=nred[:n].copy(), verdict=ver[:n].copy(),
+                    bad_mp=bmp[:r.n_bad].copy())
+
+    def MapPointCulling(self, mp, first_kf, found, visible, cur_kf, monocular=False, bad=None, apply=True):
+        """LocalMapping::MapPointCulling over mlpRecentAddedMapPoints as ids with their mnFirstKFid, mnFound and
+        mnVisible.  -> (verdict, observations): 0 keep, 1 dropped (already bad), 2 bad by found ratio, 3 bad
+        by observations, 4 dropped (old enough).  apply: the handle erases the points with verdict 2 or 3."""
+        a = [np.ascontiguousarray(x, np.int32) for x in (mp, first_kf, found, visible)]
+        n = len(a[0])
+        b = None if bad is None else np.ascontiguousarray(bad, np.uint8)
+        ver, ob = np.zeros(max(n, 1), np.int32), np.zeros(max(n, 1), np.int32)
+        r = orb_pointcull(n, *(ptr(x) if n else None for x in a), ptr(b) if b is not None and len(b) else None,
+                          0 if b is None else len(b), int(cur_kf), int(monocular), int(apply), ptr(ver), ptr(ob))
+        check(self._L.LocalMapping_MapPointCulling(self._h, C.byref(r)), "LocalMapping_MapPointCulling")
+        return ver[:n].copy(), ob[:n].copy()
 
     def enable_timing(self, on=True):
         check(self._L.Map_enable_timing(self._h, int(on)), "Map_enable_timing")

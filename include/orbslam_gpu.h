@@ -710,6 +710,82 @@ int Tracking_UpdateLocalMap_batch(ORBmatcher_h h, Map_h map, int count, orb_loca
 int Map_enable_timing(Map_h h, int on);
 int Map_last_timings(Map_h h, float* ms5);
 
+/* ---- LocalMapping::KeyFrameCulling and MapPointCulling over the Map handle -----------------
+ * The per-slot key attributes of one keyframe row, forwarded once from the KeyFrame constructor:
+ * octave[i] = mvKeysUn[i].octave; uRight = mvuRight (NULL: every observation is monocular; else
+ * slot i is stereo when uRight[i] >= 0, and its observation counts 2 in MapPoint::nObs,
+ * MapPoint.cc AddObservation / EraseObservation); depth = mvDepth and thDepth = mThDepth (NULL: no
+ * slot is far; else slot i is far when depth[i] > thDepth || depth[i] < 0, LocalMapping.cc
+ * KeyFrameCulling).  The handle keeps one byte of octave and the two bits per slot; they follow
+ * the row through repacks, and a keyframe whose keys were never set reads as octave 0,
+ * monocular, not far.  N must equal the row's slot count.  ORB_E_INVALID: an unknown id, another
+ * N.  Only octave is dereferenced before the handle is looked at. */
+int Map_SetKeyFrameKeys(Map_h h, int32_t id, int N, const uint8_t* octave, const float* uRight,
+                        const float* depth, float thDepth);
+
+/* void LocalMapping::KeyFrameCulling()                          LocalMapping.cc
+ * cand = mpCurrentKeyFrame->GetVectorCovisibleKeyFrames() as ids, examined one after another.
+ * Per candidate: id 0 or an id not live in the handle is skipped (verdict 3).  Over the row's
+ * slots that hold a point that is not bad (bad[] or gone bad earlier in this call), and unless
+ * monocular that are not far: nMPs counts them; a point with Observations() > 3 (MapPoint::nObs:
+ * 2 per stereo observation, 1 per monocular one) whose observers other than the candidate, with
+ * octave <= the slot's octave + 1, number at least 3 (the count saturates there, so the order
+ * inside mObservations is not observable) adds to nRedundant.  nRedundant > 0.9 * nMPs in double
+ * makes the candidate redundant: with not_erase (KeyFrame::mbNotErase) that only sets mbToBeErased
+ * (verdict 2, nothing changes); otherwise KeyFrame::SetBadFlag (verdict 1): in slot order
+ * MapPoint::EraseObservation of every observed slot takes 2 or 1 off the point's nObs, and a point
+ * left with nObs <= 2 runs MapPoint::SetBadFlag -- it leaves every row and is reported in bad_mp,
+ * in cull order and within a cull in ascending slot of the culled row.  Every later candidate is
+ * counted against the state the earlier culls left; nMPs / nRedundant are the counts at the moment
+ * the candidate was examined.
+ * apply != 0: on ORB_OK the handle erases the culled keyframes and the reported points, as
+ * Map_EraseKeyFrame / Map_EraseMapPoint would; apply == 0 leaves the handle as it was.  The
+ * spanning-tree repair and connection bookkeeping of KeyFrame::SetBadFlag, mpRefKF of the points
+ * and KeyFrameDatabase_erase stay with the adapter.
+ * ORB_E_CAPACITY when n_bad > cap_bad: n_bad is set, nothing is written past cap_bad and nothing
+ * is applied; call again.  ORB_E_INVALID: n < 0, a candidate named twice, a missing array.
+ * Host pointers; synchronous; runs on the handle's own stream. */
+typedef struct orb_kfcull {
+    int n;
+    const int32_t* cand;         /* n */
+    const uint8_t* not_erase;    /* n, may be NULL */
+    int monocular;               /* LocalMapping::mbMonocular */
+    const uint8_t* bad;          /* the map-point table's isBad() flags (nbad), may be NULL */
+    int nbad;
+    int cap_bad;
+    int apply;
+    int32_t* nMPs;               /* out (n) */
+    int32_t* nRedundant;         /* out (n) */
+    int32_t* verdict;            /* out (n): 0 kept, 1 SetBadFlag, 2 mbToBeErased, 3 skipped */
+    int32_t* bad_mp;             /* out (cap_bad) */
+    int n_bad;                   /* out */
+} orb_kfcull;
+int LocalMapping_KeyFrameCulling(Map_h h, orb_kfcull* r);
+
+/* void LocalMapping::MapPointCulling()                          LocalMapping.cc
+ * Per point of mlpRecentAddedMapPoints, independently, the first rule that holds: isBad() (bad[])
+ * -> verdict 1 (dropped); GetFoundRatio() = float(found) / visible < 0.25f -> 2 (SetBadFlag);
+ * (int)cur_kf - (int)first_kf >= 2 && Observations() <= cnThObs (2 when monocular, else 3) -> 3
+ * (SetBadFlag); the same difference >= 3 -> 4 (dropped); else 0 (kept).  observations (may be
+ * NULL) = MapPoint::Observations() as the handle counts it; an id the handle never saw has 0.
+ * apply != 0: the points with verdict 2 or 3 are erased as Map_EraseMapPoint would.
+ * ORB_E_INVALID: n < 0, mp[i] < 0, visible[i] <= 0, a missing array.  Host pointers; synchronous. */
+typedef struct orb_pointcull {
+    int n;
+    const int32_t* mp;           /* n: map-point ids */
+    const int32_t* first_kf;     /* n: mnFirstKFid */
+    const int32_t* found;        /* n: mnFound */
+    const int32_t* visible;      /* n: mnVisible */
+    const uint8_t* bad;          /* isBad() flags (nbad), may be NULL */
+    int nbad;
+    int32_t cur_kf;              /* mpCurrentKeyFrame->mnId */
+    int monocular;
+    int apply;
+    int32_t* verdict;            /* out (n) */
+    int32_t* observations;       /* out (n), may be NULL */
+} orb_pointcull;
+int LocalMapping_MapPointCulling(Map_h h, orb_pointcull* r);
+
 /* DBoW2::FeatureVector (std::map<NodeId, std::vector<unsigned>>) as CSR: strictly ascending
  * node ids, the feature indices of node a at feat[start[a] .. start[a+1]) in insertion order.
  * (Computed by the caller's vocabulary; ORBvoc.txt is not shipped with the reference.) */
