@@ -15,3 +15,4 @@ from .ransac import Initializer, PnPsolver, Rng, Sim3Solver  # noqa: F401
 from .vocabulary import BowVector, ORBVocabulary  # noqa: F401
 from .keyframe_database import KeyFrameDatabase  # noqa: F401
 from .map import Map  # noqa: F401
+from .loop_closing import LoopClosing  # noqa: F401

@@ -299,6 +299,8 @@ def lib():
     L.Map_SetKeyFrameKeys.argtypes = [vp, C.c_int32, i32, vp, vp, vp, f32]
     L.LocalMapping_KeyFrameCulling.argtypes = [vp, vp]
     L.LocalMapping_MapPointCulling.argtypes = [vp, vp]
+    L.LoopClosing_CorrectLoop.argtypes = [vp, vp, vp]
+    L.LoopClosing_ApplyGlobalBA.argtypes = [vp, vp, vp]
     L.orbgpu_unit_set_map_initial_capacity.argtypes = [i32, i32, i32]
     L.orbgpu_unit_set_map_chunk.argtypes = [i32]
     L.orbgpu_unit_set_map_lds_slots.argtypes = [i32]
@@ -409,6 +411,26 @@ class orb_pointcull(C.Structure):
     _fields_ = [("n", C.c_int), ("mp", C.c_void_p), ("first_kf", C.c_void_p), ("found", C.c_void_p),
                 ("visible", C.c_void_p), ("bad", C.c_void_p), ("nbad", C.c_int), ("cur_kf", C.c_int32),
                 ("monocular", C.c_int), ("apply", C.c_int), ("verdict", C.c_void_p), ("observations", C.c_void_p)]
+
+
+class orb_pointtable(C.Structure):
+    _fields_ = [("n", C.c_int), ("pos", C.c_void_p), ("normal", C.c_void_p), ("max_dist", C.c_void_p),
+                ("min_dist", C.c_void_p), ("bad", C.c_void_p), ("ref_kf", C.c_void_p)]
+
+
+class orb_loopcorrect(C.Structure):
+    _fields_ = [("nkf", C.c_int), ("kf", C.c_void_p), ("cur_kf", C.c_int32), ("Scw", C.c_void_p),
+                ("nlevels", C.c_int), ("scale_factors", C.c_void_p), ("n_kf_rows", C.c_int), ("Tcw", C.c_void_p),
+                ("pts", orb_pointtable), ("corrected_ref", C.c_void_p), ("CorrectedSim3", C.c_void_p),
+                ("NonCorrectedSim3", C.c_void_p), ("n_corrected", C.c_int32), ("n_ref_missing", C.c_int32)]
+
+
+class orb_gbaapply(C.Structure):
+    _fields_ = [("norigins", C.c_int), ("origins", C.c_void_p), ("n_kf_rows", C.c_int), ("TcwGBA", C.c_void_p),
+                ("kf_in_gba", C.c_void_p), ("Tcw", C.c_void_p), ("pts", orb_pointtable), ("posGBA", C.c_void_p),
+                ("mp_in_gba", C.c_void_p), ("TcwBefGBA", C.c_void_p), ("kf_done", C.c_void_p),
+                ("n_kf_propagated", C.c_int32), ("n_mp_gba", C.c_int32), ("n_mp_moved", C.c_int32),
+                ("depth", C.c_int32)]
 
 
 class pose_frame(C.Structure):

@@ -1,5 +1,8 @@
 // capi_handles.hpp -- the opaque C handles of include/orbslam_gpu.h (shared by the capi_*.cpp units).
 #pragma once
+#include <mutex>
+
+#include "map.hpp"
 #include "orb_extract.hpp"
 #include "orb_match.hpp"
 
@@ -9,4 +12,9 @@ struct ORBextractor_t {
 
 struct ORBmatcher_t {
     orbgpu::Matcher* m;
+};
+
+struct Map_t {
+    orbgpu::Map map;
+    std::mutex mu;   // stands for Map::mMutexMap, KeyFrame::mMutexFeatures / mMutexConnections
 };

@@ -16,11 +16,6 @@
 #include "capi_handles.hpp"
 #include "map.hpp"
 
-struct Map_t {
-    orbgpu::Map map;
-    std::mutex mu;   // stands for Map::mMutexMap, KeyFrame::mMutexFeatures / mMutexConnections
-};
-
 namespace {
 
 constexpr int kDefaultSlots = 1024, kDefaultCells = 1 << 20, kDefaultPoints = 1 << 16;

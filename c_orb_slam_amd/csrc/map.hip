@@ -18,6 +18,7 @@
 //   k_map_restore    the touched scratch entries back to idle
 #include <algorithm>
 #include <cstring>
+#include <utility>
 
 #include "map.hpp"
 #include "orb_common.hpp"
@@ -1231,6 +1232,47 @@ int Map::cull_points(const MapPtCull& c) {
     std::memcpy(c.verdict, io.data() + o_out, 4 * (size_t)n);
     if (c.observations) std::memcpy(c.observations, io.data() + o_out + w, 4 * (size_t)n);
     return leave(s);
+}
+
+int Map::begin_view(hipStream_t s, MapView& v) {
+    if (int e = join(s)) return e;
+    if (int e = sync_device(s)) return e;
+    if (int e = sync_cull(s)) return e;
+    v.slots = d_slots_;
+    v.mp = d_mp_;
+    v.obs = d_obs_;
+    v.oct = d_oct_;
+    v.pt_start = d_pt_start_;
+    v.pt_obs = d_pt_obs_;
+    v.npts = n_live_dev_ > 0 ? npts_ : 0;   // without a live row the index was never filled
+    return 0;
+}
+
+// Three-colour depth-first search over the children lists, without recursion (a chain may be as
+// long as the map).  Children that are not live are skipped, as every reader skips them.
+bool Map::children_cyclic() const {
+    std::vector<uint8_t> colour(slots_.size(), 0);   // 0 new, 1 on the path, 2 done
+    std::vector<std::pair<int, size_t>> path;
+    for (const auto& kv : slot_of_) {
+        if (colour[kv.second]) continue;
+        colour[kv.second] = 1;
+        path.emplace_back(kv.second, 0);
+        while (!path.empty()) {
+            const int sl = path.back().first;
+            const std::vector<int32_t>& ch = nb_[sl].children;
+            if (path.back().second == ch.size()) {
+                colour[sl] = 2;
+                path.pop_back();
+                continue;
+            }
+            const int c = slot_of(ch[path.back().second++]);
+            if (c < 0 || colour[c] == 2) continue;
+            if (colour[c] == 1) return true;
+            colour[c] = 1;
+            path.emplace_back(c, 0);
+        }
+    }
+    return false;
 }
 
 }  // namespace orbgpu

@@ -101,6 +101,17 @@ struct MapPtCull {
     int32_t* observations;      // out n or null
 };
 
+// the handle's device state as another unit's kernels read it (Map::begin_view)
+struct MapView {
+    const MapSlotDev* slots;
+    const int32_t* mp;          // cell pools: map-point id, observed, octave
+    const uint8_t* obs;
+    const uint8_t* oct;
+    const int32_t* pt_start;    // npts + 1
+    const uint32_t* pt_obs;     // per point the observing cells, slot * 4096 + index, in no order
+    int32_t npts;
+};
+
 class Map {
 public:
     ~Map();
@@ -143,6 +154,17 @@ public:
     // Tracking::UpdateLocalMap for `count` frames queued on `s`; d_frames = the frames in device
     // memory (valid until the work is done), h_frames = the same on the host.
     int update_local(hipStream_t s, int count, const MapLocalDev* d_frames, const MapLocalDev* h_frames);
+
+    // The relation for the kernels of another unit (loopcorrect.hip), on stream `s`: the stream is
+    // ordered behind the handle's last query, the device state brought up to date (rows, inverse
+    // index, octaves and the point -> cells index), and `v` filled.  end_view(s) closes the query.
+    int begin_view(hipStream_t s, MapView& v);
+    int end_view(hipStream_t s) { return leave(s); }
+    int n_ids() const { return nid_; }   // largest keyframe id seen + 1
+    int row_size(int slot) const { return slots_[slot].n; }
+    const std::vector<int32_t>& children(int slot) const { return nb_[slot].children; }
+    // a keyframe that is its own descendant over the live keyframes' children lists
+    bool children_cyclic() const;
 
     void set_chunk(int frames) { chunk_ = frames; }
     void set_lds_slots(int n) { lds_slots_ = n; }

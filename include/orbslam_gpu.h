@@ -786,6 +786,101 @@ typedef struct orb_pointcull {
 } orb_pointcull;
 int LocalMapping_MapPointCulling(Map_h h, orb_pointcull* r);
 
+/* ---- LoopClosing's map correction over the Map handle -------------------------------------
+ * The two steps of the loop-closing thread that move the map: the first half of
+ * LoopClosing::CorrectLoop and the tail of LoopClosing::RunGlobalBundleAdjustment
+ * (src/LoopClosing.cc).  Both work on the caller's tables: the keyframe pose table Tcw
+ * (n_kf_rows x 16 floats, row-major, indexed by mnId; every id the handle has seen must be below
+ * n_kf_rows) and the map-point table indexed by the map-point row, as
+ * Tracking_UpdateLocalMap_batch gathers from it.
+ * Pointer space: every array marked (table) is in the pointer space of
+ * ORBmatcher_set_device_pointers(h); lists, counts, the Sim3 arrays and the structs are host.
+ * Both calls run on ORBmatcher_stream(h), hold the map handle's lock and return when their
+ * results are in place.  A matcher in deferred mode answers ORB_E_INVALID.
+ * Arithmetic: a cv::Mat product is one cv::gemm (float operands, the sum over k ascending in
+ * double, one rounding to float); SetPose(Tcw) forms Rwc = Rcw^T and Ow = -Rwc * tcw as a gemm with
+ * alpha -1; g2o::Sim3(R, t, 1) widens to double and takes Eigen's Quaterniond(Matrix3d) without
+ * normalising; Sim3 products, inverse and map are g2o's (sim3.h); toCvMat is one cast per entry.
+ * ORB_E_INVALID, before any table is written: a null required array, a listed keyframe that is not
+ * live in the handle or is named twice, an id >= n_kf_rows, a non-finite Scw or s <= 0, a cycle in
+ * the children relation of Map_SetNeighbours.  A call with a NULL handle answers ORB_E_NODEVICE
+ * where no device is visible (ORB_E_INVALID otherwise). */
+typedef struct orb_pointtable {
+    int n;                       /* rows */
+    float* pos;                  /* (table) n x 3, in/out */
+    float* normal;               /* (table) n x 3, in/out (CorrectLoop) */
+    float* max_dist;             /* (table) n, in/out (CorrectLoop) */
+    float* min_dist;             /* (table) n, in/out (CorrectLoop) */
+    const uint8_t* bad;          /* (table) n: isBad(), may be NULL */
+    const int32_t* ref_kf;       /* (table) n: mpRefKF's id, -1 = none */
+} orb_pointtable;
+
+/* void LoopClosing::CorrectLoop(), from CorrectedSim3[mpCurrentKF] = mg2oScw to the end of the
+ * loop over CorrectedSim3.  The listed keyframes are processed in ascending id (the id-order rule
+ * for the KeyFrameAndPose map), whatever order kf[] has.
+ * 1. Per listed keyframe i, from the old poses: NonCorrected[i] = Sim3(Riw, tiw, 1);
+ *    Corrected[cur] = Scw, otherwise Tic = Tiw * Twc(cur), Corrected[i] = Sim3(Ric, tic, 1) * Scw.
+ * 2. Every point held in any slot of a listed keyframe (observed or not) that is not bad is
+ *    corrected once, by the listed keyframe of lowest id that holds it; corrected_ref[p] takes that
+ *    id (mnCorrectedReference).  Other rows of corrected_ref are untouched.  A held id >= pts.n is
+ *    skipped.
+ * 3. pos[p] = (float) Corrected[k]^-1.map(NonCorrected[k].map((double) pos[p])).
+ * 4. MapPoint::UpdateNormalAndDepth of each corrected point with the new position over its
+ *    observations in the handle, taken in ascending keyframe id.  The camera centre of an observer
+ *    (and of ref_kf[p]) comes from its corrected pose when it is a listed keyframe processed before
+ *    the corrector, else from its old pose.  ref_scale = scale_factors[octave of ref_kf's observing
+ *    slot] (Map_SetKeyFrameKeys), ref_scale_top = scale_factors[nlevels - 1].  A point without
+ *    observations keeps normal / max_dist / min_dist.  So does a point whose ref_kf is -1 or not
+ *    among its observers, or whose octave is >= nlevels; those count in n_ref_missing (the
+ *    reference would read keypoint 0 there).
+ * 5. Tcw[i] = [R(Corrected[i]) | t * (1 / s); 0 0 0 1] for every listed i.
+ * KeyFrame::UpdateConnections of the listed keyframes stays with
+ * KeyFrame_UpdateConnections_batch; the relation is not changed here. */
+typedef struct orb_loopcorrect {
+    int nkf;
+    const int32_t* kf;           /* nkf: mvpCurrentConnectedKFs with the current keyframe */
+    int32_t cur_kf;
+    const double* Scw;           /* 8: mg2oScw as q xyzw, t, s (the layout of essgraph_problem) */
+    int nlevels;
+    const float* scale_factors;  /* nlevels: mvScaleFactors */
+    int n_kf_rows;
+    float* Tcw;                  /* (table) n_kf_rows x 16, in/out */
+    orb_pointtable pts;
+    int32_t* corrected_ref;      /* (table) pts.n, in/out */
+    double* CorrectedSim3;       /* out nkf x 8, in the order of kf[] */
+    double* NonCorrectedSim3;    /* out nkf x 8, in the order of kf[] */
+    int32_t n_corrected, n_ref_missing;   /* out */
+} orb_loopcorrect;
+int LoopClosing_CorrectLoop(ORBmatcher_h h, Map_h map, orb_loopcorrect* C);
+
+/* void LoopClosing::RunGlobalBundleAdjustment(nLoopKF), the write-back after the optimisation:
+ * the spanning tree is walked breadth first from `origins` (mvpKeyFrameOrigins) over the handle's
+ * children; ids not live in the handle are skipped, as bad keyframes are.  A child without
+ * kf_in_gba takes TcwGBA[child] = (Tcw[child] * Twc[parent]) * TcwGBA[parent] (two gemms, the old
+ * Tcw) and counts as in the BA from then on; a child with kf_in_gba keeps its row.  Every reached
+ * keyframe then gets TcwBefGBA = Tcw and Tcw = TcwGBA; unreached keyframes are untouched.  An
+ * origin that is live but not in the BA is ORB_E_INVALID.
+ * Every point that is not bad: with mp_in_gba, pos = posGBA; otherwise with r = ref_kf[p] reached,
+ * Xc = Rcw_bef[r] * X + tcw_bef[r], pos = Rwc[r] * Xc + Ow[r] from SetPose(TcwGBA[r]) (one gemm
+ * each); with r = -1 or unreached the point is untouched.  No UpdateNormalAndDepth follows.
+ * n_kf_propagated = the keyframes that took a propagated pose, depth = the longest chain of them
+ * (the number of dependent steps run), n_mp_gba / n_mp_moved = the points of the two kinds. */
+typedef struct orb_gbaapply {
+    int norigins;
+    const int32_t* origins;
+    int n_kf_rows;
+    float* TcwGBA;               /* (table) n_kf_rows x 16: read where kf_in_gba, written where propagated */
+    const uint8_t* kf_in_gba;    /* (table) n_kf_rows: mnBAGlobalForKF == nLoopKF */
+    float* Tcw;                  /* (table) n_kf_rows x 16, in/out */
+    orb_pointtable pts;          /* pos in/out, bad, ref_kf; the other arrays are not read */
+    const float* posGBA;         /* (table) pts.n x 3: mPosGBA */
+    const uint8_t* mp_in_gba;    /* (table) pts.n: mnBAGlobalForKF == nLoopKF */
+    float* TcwBefGBA;            /* (table) out n_kf_rows x 16, may be NULL: the rows of reached keyframes */
+    uint8_t* kf_done;            /* (table) out n_kf_rows, may be NULL: 1 = reached */
+    int32_t n_kf_propagated, n_mp_gba, n_mp_moved, depth;   /* out */
+} orb_gbaapply;
+int LoopClosing_ApplyGlobalBA(ORBmatcher_h h, Map_h map, orb_gbaapply* G);
+
 /* DBoW2::FeatureVector (std::map<NodeId, std::vector<unsigned>>) as CSR: strictly ascending
  * node ids, the feature indices of node a at feat[start[a] .. start[a+1]) in insertion order.
  * (Computed by the caller's vocabulary; ORBvoc.txt is not shipped with the reference.) */
