@@ -522,44 +522,61 @@ __global__ void __launch_bounds__(256) k_blur7(const uint8_t* __restrict__ pyr, 
     }
 }
 
-__device__ __forceinline__ int min3(int a, int b, int c) { return min(min(a, b), c); }
-__device__ __forceinline__ int max3(int a, int b, int c) { return max(max(a, b), c); }
+constexpr int FC_LD = 76;      // LDS row pitch of the cell ROI (19 dwords: odd bank stride)
+constexpr int FC_MAXR = 70;    // max ROI rows/cols supported (wCell/hCell <= 64)
+
+typedef short short2v __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ short2v pk16(int lo, int hi) {
+    short2v r;
+    r.x = (short)lo;
+    r.y = (short)hi;
+    return r;
+}
+__device__ __forceinline__ uint32_t pk_bits(short2v v) { return __builtin_bit_cast(uint32_t, v); }
+__device__ __forceinline__ short2v pk_min(short2v a, short2v b) { return __builtin_elementwise_min(a, b); }
+__device__ __forceinline__ short2v pk_max(short2v a, short2v b) { return __builtin_elementwise_max(a, b); }
 
 // FAST-9/16 score S = max(A,B)-1 (OpenCV cornerScore<16>): A/B = best
 // contiguous-9 dark/bright contrast.  A pixel is a corner at threshold t
 // iff S >= t, and its stored score is then S (see oracle/ocv_semantics.c).
-__device__ __forceinline__ int fast_score_lds(const uint8_t* p, int ld) {
-    const int v = p[0];
-    int d[16];
-    d[0] = v - p[3 * ld];       d[1] = v - p[3 * ld + 1];   d[2] = v - p[2 * ld + 2];
-    d[3] = v - p[ld + 3];       d[4] = v - p[3];            d[5] = v - p[-ld + 3];
-    d[6] = v - p[-2 * ld + 2];  d[7] = v - p[-3 * ld + 1];  d[8] = v - p[-3 * ld];
-    d[9] = v - p[-3 * ld - 1];  d[10] = v - p[-2 * ld - 2]; d[11] = v - p[-ld - 3];
-    d[12] = v - p[-3];          d[13] = v - p[ld - 3];      d[14] = v - p[2 * ld - 2];
-    d[15] = v - p[3 * ld - 1];
-    int mn2[16], mx2[16];
+// Two pixels at once in packed 16-bit lanes (pixel a low half, pixel b high half), LDS row
+// pitch FC_LD: every intermediate of the min/max network is one of the 16 ring differences, so
+// nothing leaves [-255, 255] and the packed result is the 32-bit one.  Returns max(S, 0) per half.
+__device__ __forceinline__ short2v fast_score2_lds(const uint8_t* pa, const uint8_t* pb) {
+    constexpr int ld = FC_LD;
+    constexpr int ring[16] = {3 * ld,      3 * ld + 1,  2 * ld + 2,  ld + 3,  3,  -ld + 3, -2 * ld + 2, -3 * ld + 1,
+                              -3 * ld,     -3 * ld - 1, -2 * ld - 2, -ld - 3, -3, ld - 3,  2 * ld - 2,  3 * ld - 1};
+    const short2v v = pk16(pa[0], pb[0]);
+    short2v d[16], mn2[16], mx2[16];
+#pragma unroll
+    for (int k = 0; k < 16; k++) d[k] = v - pk16(pa[ring[k]], pb[ring[k]]);
 #pragma unroll
     for (int k = 0; k < 16; k++) {
-        mn2[k] = min(d[k], d[(k + 1) & 15]);
-        mx2[k] = max(d[k], d[(k + 1) & 15]);
+        mn2[k] = pk_min(d[k], d[(k + 1) & 15]);
+        mx2[k] = pk_max(d[k], d[(k + 1) & 15]);
     }
     // arcs k and k+1 (k even) share d[k+1..k+8]: max over the pair of the arc minima is
     // min(shared minimum, max(d[k], d[k+9])) (and the mirrored form for the maxima), so the
     // 16 arcs cost 8 shared reductions
-    int A = -1000, M = 1000;
+    // (there is no packed min3: the shared minimum of d[k+1..k+8] is two 4-wide halves, each
+    // used by arcs k and k+4)
+    short2v mn4[8], mx4[8];
+#pragma unroll
+    for (int k = 0; k < 8; k++) {
+        mn4[k] = pk_min(mn2[2 * k + 1], mn2[(2 * k + 3) & 15]);
+        mx4[k] = pk_max(mx2[2 * k + 1], mx2[(2 * k + 3) & 15]);
+    }
+    short2v A = pk16(-1000, -1000), M = pk16(1000, 1000);
 #pragma unroll
     for (int k = 0; k < 16; k += 2) {
-        const int smin = min(min3(mn2[(k + 1) & 15], mn2[(k + 3) & 15], mn2[(k + 5) & 15]), mn2[(k + 7) & 15]);
-        const int smax = max(max3(mx2[(k + 1) & 15], mx2[(k + 3) & 15], mx2[(k + 5) & 15]), mx2[(k + 7) & 15]);
-        A = max(A, min(smin, max(d[k], d[(k + 9) & 15])));
-        M = min(M, max(smax, min(d[k], d[(k + 9) & 15])));
+        const short2v smin = pk_min(mn4[k >> 1], mn4[((k >> 1) + 2) & 7]);
+        const short2v smax = pk_max(mx4[k >> 1], mx4[((k >> 1) + 2) & 7]);
+        A = pk_max(A, pk_min(smin, pk_max(d[k], d[(k + 9) & 15])));
+        M = pk_min(M, pk_max(smax, pk_min(d[k], d[(k + 9) & 15])));
     }
-    const int B = -M;
-    return max(A, B) - 1;
+    const short2v B = pk16(0, 0) - M;
+    return pk_max(pk_max(A, B) - pk16(1, 1), pk16(0, 0));
 }
-
-constexpr int FC_LD = 76;      // LDS row pitch of the cell ROI (19 dwords: odd bank stride)
-constexpr int FC_MAXR = 70;    // max ROI rows/cols supported (wCell/hCell <= 64)
 
 // Necessary condition for FAST-9 at threshold t (S >= t): a 9-arc contains two consecutive
 // compass points (0,4), (4,8), (8,12) or (12,0), all brighter than v+t or all darker than v-t.
@@ -577,14 +594,6 @@ __device__ __forceinline__ bool fast_pretest(const uint8_t* p, int ld, int t) {
 // so the sign bits of the packed differences are the negated comparisons, and
 // fail = !dark && !bright = ((na & nc) | (nb & nd)) & ((ba & bc) | (bb & bd)) on those bits.
 // Bit 15 / bit 31 of the result set: row A / row B fails.
-typedef short short2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ short2v pk16(int lo, int hi) {
-    short2v r;
-    r.x = (short)lo;
-    r.y = (short)hi;
-    return r;
-}
-__device__ __forceinline__ uint32_t pk_bits(short2v v) { return __builtin_bit_cast(uint32_t, v); }
 __device__ __forceinline__ uint32_t fast_pretest2_fail(const uint8_t* pa, const uint8_t* pb, int ld, short2v T1) {
     const short2v v = pk16(pa[0], pb[0]);
     const short2v a = pk16(pa[3 * ld], pb[3 * ld]), b = pk16(pa[3], pb[3]);
@@ -608,10 +617,6 @@ __device__ __forceinline__ void mask_scan64(const uint64_t* masks, int n, int* o
     if (lane == 63) off[64] = incl;
 }
 
-__device__ __forceinline__ int sel4(int k, int a0, int a1, int a2, int a3) {
-    return k == 0 ? a0 : k == 1 ? a1 : k == 2 ? a2 : a3;
-}
-
 // One workgroup (4 waves) per (cell group, image): up to 2 x 2 cells whose ROIs tile one union
 // ROI (CellGroup), so the staging, the syncs and the scans are shared by up to four cells.
 // Every pixel loop is division-free.
@@ -619,28 +624,34 @@ __device__ __forceinline__ int sel4(int k, int a0, int a1, int a2, int a3) {
 //   pretest  FAST-9 necessary condition at min(iniTh, minTh) per detection pixel: lanes over
 //            the union's detection columns (<= 64), one ballot per detection row
 //   list     survivors, ~10 % of the pixels, cell by cell (TL, TR, BL, BR) and raster order
-//            inside a cell (row-count scans): cell k's are list entries [lb_k, lb_k+1)
-//   score    OpenCV cornerScore<16> for the list only (pixels failing the pretest score < th)
+//            inside a cell (row-count scans): cell k's are list entries [lb_k, lb_k+1); a lane
+//            places the survivors of 4 columns
+//   score    OpenCV cornerScore<16> for the list only (pixels failing the pretest score < th),
+//            two entries per lane in packed 16-bit halves
 //   NMS      per entry and for BOTH thresholds: keep = S >= th && S > every 8-neighbour's
 //            (S >= th ? S : 0) <=> S >= th && S > every 8-neighbour's S (one local-maximum test
 //            for both thresholds), a neighbour outside the entry's own cell counting 0 (the
-//            reference runs FAST on each cell's ROI alone, ORBextractor.cc:794-829)
+//            reference runs FAST on each cell's ROI alone, ORBextractor.cc:794-829): the cells'
+//            scores are stored one zero row / column apart, so the eight reads need no test
 //   output   per cell: its iniTh keeps if it has any, else its minTh keeps (the retry of
-//            ORBextractor.cc:810-815), compacted in list order into the cell's slots
+//            ORBextractor.cc:810-815), compacted in list order into the cell's slots; the
+//            cell's constants come from a 4-row LDS table, not from selects per keep
 __global__ void __launch_bounds__(256) k_fast_cells(const uint8_t* __restrict__ pyr, size_t img_bytes,
                                                     const CellGroup* __restrict__ groups, int iniTh, int minTh,
                                                     uint32_t* __restrict__ slots, size_t slots_per_image,
                                                     int* __restrict__ counts, int ncells,
                                                     const int* __restrict__ work) {
-    __shared__ uint32_t s_img32[FC_MAXR * FC_LD / 4];
+    __shared__ __attribute__((aligned(16))) uint32_t s_img32[FC_MAXR * FC_LD / 4];
     __shared__ uint32_t s_sc32[FC_MAXR * FC_LD / 4];
-    __shared__ uint16_t s_list[64 * 64];
+    __shared__ uint32_t s_list32[64 * 64 / 2];   // 16-bit entries, read in pairs by the scoring
     __shared__ uint64_t s_mask[64], s_khi[64];
     __shared__ int s_off[65], s_offR[64];
     __shared__ int s_lb[5];
     uint8_t* s_img = reinterpret_cast<uint8_t*>(s_img32);
     uint8_t* s_sc = reinterpret_cast<uint8_t*>(s_sc32);
+    uint16_t* s_list = reinterpret_cast<uint16_t*>(s_list32);
     uint64_t* s_klo = reinterpret_cast<uint64_t*>(s_img32);   // the ROI is dead after scoring
+    int* s_tab = reinterpret_cast<int*>(s_img32 + 128);       // after s_klo: 4 cells x 8 ints, the output table
     // work order (Extractor::build_work): workgroup g runs on XCD g % 8; whole group rows of an
     // image go to one XCD (rows dealt round-robin), so horizontally adjacent groups -- which
     // share ROI halo columns and 128-B lines -- hit that XCD's L2 instead of being fetched
@@ -766,19 +777,46 @@ __global__ void __launch_bounds__(256) k_fast_cells(const uint8_t* __restrict__ 
     }
     __syncthreads();
     const int nl = s_lb[4];
-    for (int i = wid; i < dr; i += 4) {
-        const uint64_t m = s_mask[i];
-        if ((m >> lane) & 1ull) {
-            const uint64_t below = m & ((1ull << lane) - 1ull);
-            const int pos = lane < cs ? s_off[i] + (int)__popcll(below) : s_offR[i] + (int)__popcll(below & ~Lm);
-            s_list[pos] = (uint16_t)(((3 + i) << 8) | (3 + lane));
+    {
+        // 4 detection columns per lane as in the pretest (16 lanes per row, 16 rows per pass of
+        // the workgroup).  The nibble's columns below sj belong to the left cell: those entries
+        // follow the row's left run (bL), the others its right run (bR), each at its rank among
+        // the nibble's set bits (bR is taken back by the nibble's left bits for that).
+        const int rho = lane >> 4, L = lane & 15;
+        const int sj = min(max(cs - 4 * L, 0), 4);
+        const uint32_t lnib = (1u << sj) - 1u;
+        const uint64_t lowm = (1ull << (4 * L)) - 1ull, lowR = lowm & ~Lm;
+        for (int i = 4 * wid + rho; i < dr; i += 16) {
+            const uint64_t m = s_mask[i];
+            const uint32_t nib = (uint32_t)(m >> (4 * L)) & 0xfu;
+            if (nib) {
+                // sj > 0 => every column below the nibble is a left one
+                const int bL = s_off[i] + (int)__popcll(m & lowm);
+                const int bR = s_offR[i] + (int)__popcll(m & lowR) - (int)__popc(nib & lnib);
+                const uint32_t e0 = (uint32_t)(((3 + i) << 8) | (3 + 4 * L));
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    if ((nib >> j) & 1u)
+                        s_list[(j < sj ? bL : bR) + (int)__popc(nib & ((1u << j) - 1u))] = (uint16_t)(e0 + j);
+            }
         }
     }
     __syncthreads();
-    for (int k = tid; k < nl; k += 256) {
-        const int rc = s_list[k], r = rc >> 8, cc = rc & 0xff;
-        const int sc = fast_score_lds(&s_img[r * FC_LD + mis + cc], FC_LD);
-        s_sc[r * FC_LD + cc] = (uint8_t)max(sc, 0);
+    // The scores of the (up to) four cells are kept apart by one zero row and one zero column
+    // (entry (r, c) at row r + [bottom cell], column c + [right cell] of s_sc; the frame around
+    // the detection pixels is zero as well), so every neighbour outside an entry's own cell
+    // reads 0 without a test.
+    auto sc_at = [&](int r, int cc) { return (r + (r >= 3 + rs)) * FC_LD + cc + (cc >= 3 + cs); };
+    // list entries 2p and 2p+1 (one dword of the list) per lane, in packed 16-bit halves; the odd
+    // last entry is paired with itself and that half is not stored
+    for (int p = tid; 2 * p < nl; p += 256) {
+        const uint32_t rc2 = s_list32[p];
+        const bool two = 2 * p + 1 < nl;
+        const int rca = rc2 & 0xffff, rcb = two ? (int)(rc2 >> 16) : rca;
+        const int ra = rca >> 8, ca = rca & 0xff, rb = rcb >> 8, cb = rcb & 0xff;
+        const short2v sc = fast_score2_lds(&s_img[ra * FC_LD + mis + ca], &s_img[rb * FC_LD + mis + cb]);
+        s_sc[sc_at(ra, ca)] = (uint8_t)sc.x;
+        if (two) s_sc[sc_at(rb, cb)] = (uint8_t)sc.y;
     }
     __syncthreads();
     ORBGPU_PROF_MARK(2);
@@ -788,16 +826,10 @@ __global__ void __launch_bounds__(256) k_fast_cells(const uint8_t* __restrict__ 
         bool khi = false, klo = false;
         if (k < nl) {
             const int rc = s_list[k], r = rc >> 8, cc = rc & 0xff;
-            const int s = s_sc[r * FC_LD + cc];
-            const bool bot = r >= 3 + rs, rgt = cc >= 3 + cs;
-            // the entry's own cell: detection rows [rlo, rhi), columns [clo, chi)
-            const int rlo = bot ? 3 + rs : 3, rhi = bot ? 3 + dr : 3 + rs;
-            const int clo = rgt ? 3 + cs : 3, chi = rgt ? 3 + dc : 3 + cs;
-            const bool up = r - 1 >= rlo, dn = r + 1 < rhi, lf = cc - 1 >= clo, rt = cc + 1 < chi;
-            const uint8_t* q = &s_sc[r * FC_LD + cc];
-            const int n0 = (up && lf) ? q[-FC_LD - 1] : 0, n1 = up ? q[-FC_LD] : 0, n2 = (up && rt) ? q[-FC_LD + 1] : 0;
-            const int n3 = lf ? q[-1] : 0, n4 = rt ? q[1] : 0;
-            const int n5 = (dn && lf) ? q[FC_LD - 1] : 0, n6 = dn ? q[FC_LD] : 0, n7 = (dn && rt) ? q[FC_LD + 1] : 0;
+            const uint8_t* q = &s_sc[sc_at(r, cc)];
+            const int s = q[0];
+            const int n0 = q[-FC_LD - 1], n1 = q[-FC_LD], n2 = q[-FC_LD + 1], n3 = q[-1], n4 = q[1];
+            const int n5 = q[FC_LD - 1], n6 = q[FC_LD], n7 = q[FC_LD + 1];
             // for s >= th a neighbour below th (stored as 0 in the reference's score row) is below
             // s as well, so S > (n >= th ? n : 0) for every n <=> S > max n: one comparison
             // serves both thresholds
@@ -832,28 +864,35 @@ __global__ void __launch_bounds__(256) k_fast_cells(const uint8_t* __restrict__ 
             const int y = __shfl_up(incl, o, 64);
             if (lane >= o) incl += y;
         }
-        s_off[lane] = incl - cnt;
-        if (lane == 63) s_off[64] = incl;
+        const int excl = incl - cnt;
+        s_off[lane] = excl;
+        // lane t <= 4: the keeps before list position s_lb[t], cell t's first entry (t = 4: all
+        // keeps), from the chunk that holds it; cell t's row of the output table and its count
+        const int p = s_lb[min(lane, 4)], c = p >> 6, o = p & 63;
+        const int ex_c = __shfl(excl, c & 63, 64);
+        const uint64_t fin_c = __shfl(fin, c & 63, 64);
+        const int all = __shfl(incl, 63, 64);
+        const int bef = c >= 64 ? all : ex_c + (int)__popcll(fin_c & ((1ull << o) - 1ull));
+        const int nxt = __shfl_down(bef, 1, 64);
+        if (lane < 4) {
+            if (g.cell[lane] >= 0) cnt_out[g.cell[lane]] = min(nxt - bef, g.cap[lane]);
+            *reinterpret_cast<int4*>(&s_tab[8 * lane]) = make_int4(bef, g.cap[lane], g.xadd[lane], g.yadd[lane]);
+            s_tab[8 * lane + 4] = g.slot_off[lane];
+        }
     }
     __syncthreads();
-    // keeps before list position p
-    auto before = [&](int p) {
-        const int c = p >> 6, o = p & 63;
-        return s_off[c] + (o ? (int)__popcll(s_mask[c] & ((1ull << o) - 1ull)) : 0);
-    };
-    if (tid < 4 && g.cell[tid] >= 0) cnt_out[g.cell[tid]] = min(before(s_lb[tid + 1]) - before(s_lb[tid]), g.cap[tid]);
     uint32_t* out = slots + (size_t)b * slots_per_image;
     for (int ch = wid; ch < nch; ch += 4) {
         const uint64_t m = s_mask[ch];
         if ((m >> lane) & 1ull) {
             const int rc = s_list[ch * 64 + lane], r = rc >> 8, cc = rc & 0xff;
             const int k = (r >= 3 + rs) * 2 + (cc >= 3 + cs);
-            const int pos = s_off[ch] + __popcll(m & ((1ull << lane) - 1ull)) - before(sel4(k, s_lb[0], s_lb[1], s_lb[2], s_lb[3]));
-            if (pos < sel4(k, g.cap[0], g.cap[1], g.cap[2], g.cap[3])) {
-                const uint32_t sv = s_sc[r * FC_LD + cc];
-                const uint32_t xr = (uint32_t)(cc + sel4(k, g.xadd[0], g.xadd[1], g.xadd[2], g.xadd[3]));
-                const uint32_t yr = (uint32_t)(r + sel4(k, g.yadd[0], g.yadd[1], g.yadd[2], g.yadd[3]));
-                out[sel4(k, g.slot_off[0], g.slot_off[1], g.slot_off[2], g.slot_off[3]) + pos] = (sv << 24) | (yr << 12) | xr;
+            const int4 t = *reinterpret_cast<const int4*>(&s_tab[8 * k]);   // keeps before the cell, cap, xadd, yadd
+            const int pos = s_off[ch] + __popcll(m & ((1ull << lane) - 1ull)) - t.x;
+            if (pos < t.y) {
+                const uint32_t sv = s_sc[sc_at(r, cc)];
+                const uint32_t xr = (uint32_t)(cc + t.z), yr = (uint32_t)(r + t.w);
+                out[s_tab[8 * k + 4] + pos] = (sv << 24) | (yr << 12) | xr;
             }
         }
     }
