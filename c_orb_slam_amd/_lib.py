@@ -263,6 +263,8 @@ def lib():
     L.orbgpu_unit_sim3.argtypes = [i32, i32, vp, vp, vp, vp]
     L.orbgpu_unit_essgraph_stage.argtypes = [vp, C.c_double, vp]
     L.orbgpu_unit_set_ess_dense_max.argtypes = [i32]
+    L.orbgpu_unit_se3.argtypes = [i32, i32, vp, vp, vp]
+    L.orbgpu_unit_pose_stage.argtypes = [vp, vp, C.c_double, i32, vp]
     L.orbgpu_debug_prof.argtypes = [vp]
     L.orbgpu_debug_prof_match.argtypes = [vp]
     L.orbgpu_debug_prof_extract.argtypes = [vp]
@@ -444,6 +446,14 @@ class pose_problem(C.Structure):
     _fields_ = [("N", C.c_int), ("Tcw", C.c_void_p), ("has_mp", C.c_void_p), ("Xw", C.c_void_p),
                 ("obs", C.c_void_p), ("inv_sigma2", C.c_void_p), ("fx", C.c_float), ("fy", C.c_float),
                 ("cx", C.c_float), ("cy", C.c_float), ("bf", C.c_float)]
+
+
+class pose_stage(C.Structure):
+    _fields_ = [("ne", C.c_int), ("nA", C.c_int), ("ok", C.c_int), ("keypoint", C.c_void_p), ("T0", C.c_void_p),
+                ("err", C.c_void_p), ("chi2e", C.c_void_p), ("rho", C.c_void_p), ("J", C.c_void_p),
+                ("terms", C.c_void_p), ("sums", C.c_void_p), ("x", C.c_void_p), ("T_trial", C.c_void_p),
+                ("chi2e_trial", C.c_void_p), ("rho_trial", C.c_void_p), ("chi2_class", C.c_void_p),
+                ("Tcw_trial", C.c_void_p), ("chi2_trial", C.c_double), ("scale", C.c_double)]
 
 
 class sim3opt_problem(C.Structure):

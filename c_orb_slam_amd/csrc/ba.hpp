@@ -209,6 +209,10 @@ struct PoseProbDev;
 
 // Optimizer::PoseOptimization for a batch of frames: one persistent workgroup per frame.
 struct PoseProbDev;
+// Test-only entries (include/orbslam_gpu.h orbgpu_unit_se3, orbgpu_unit_pose_stage), pose_opt.hip
+int pose_unit_se3(int op, int n, const void* a, const void* b, void* out);
+int pose_stage_run(const pose_problem* P, const uint8_t* flags, double lambda, int threads, pose_stage* out);
+
 class PoseEngine {
 public:
     ~PoseEngine();

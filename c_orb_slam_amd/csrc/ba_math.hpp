@@ -177,8 +177,9 @@ __device__ __forceinline__ void se3_exp(const double* upd, Se3& out) {
     se3_normalize(out);
 }
 
-// Converter::toSE3Quat(Tcw) and back (row-major 4x4 float), on the host
-inline void host_se3_from_Tcw(const float* T, Se3& o) {
+// Converter::toSE3Quat(Tcw) and back (row-major 4x4 float): one sequence for the host entries,
+// k_pose_pack, k_pose_opt's write-back and the unit entry orbgpu_unit_se3
+HD void se3_from_Tcw(const float* T, Se3& o) {
     double R[9];
     for (int r = 0; r < 3; r++)
         for (int c = 0; c < 3; c++) R[r * 3 + c] = (double)T[r * 4 + c];
@@ -188,7 +189,7 @@ inline void host_se3_from_Tcw(const float* T, Se3& o) {
     se3_normalize(o);
 }
 
-inline void host_se3_to_Tcw(const Se3& s, float* T) {
+HD void se3_to_Tcw(const Se3& s, float* T) {
     double R[9];
     quat_to_R(s.q, R);
     for (int r = 0; r < 3; r++) {
@@ -198,6 +199,9 @@ inline void host_se3_to_Tcw(const Se3& s, float* T) {
     T[12] = T[13] = T[14] = 0.f;
     T[15] = 1.f;
 }
+
+inline void host_se3_from_Tcw(const float* T, Se3& o) { se3_from_Tcw(T, o); }
+inline void host_se3_to_Tcw(const Se3& s, float* T) { se3_to_Tcw(s, T); }
 
 // the diagonal entries of a 6x6 upper triangle packed by rows (21 entries)
 constexpr int DIAG21[6] = {0, 6, 11, 15, 18, 20};

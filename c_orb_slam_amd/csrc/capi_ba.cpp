@@ -1,5 +1,6 @@
 // capi_ba.cpp -- extern "C" Optimizer_LocalBundleAdjustment (include/orbslam_gpu.h).
 // Replaces ORB_SLAM2::Optimizer::LocalBundleAdjustment (reference src/Optimizer.cc:453-778).
+#include <cmath>
 #include <algorithm>
 #include <atomic>
 #include <cstring>
@@ -231,6 +232,24 @@ int Optimizer_PoseOptimization_batch_device(int count, const pose_problem* P, fl
     if (rc) return rc == -4 ? ORB_E_NODEVICE : ORB_E_HIP;
     const int r = e->run_device(count, P, Tcw_out, outlier, ninliers);
     if (r == -3) return ORB_E_CAPACITY;
+    return r ? ORB_E_HIP : ORB_OK;
+}
+
+int orbgpu_unit_se3(int op, int n, const void* a, const void* b, void* out) {
+    if (op < 0 || op > 4 || n < 0) return ORB_E_INVALID;
+    if (n > 0 && (!a || !out || ((op == 1 || op == 2) && !b))) return ORB_E_INVALID;
+    const int r = orbgpu::pose_unit_se3(op, n, a, b, out);
+    if (r == -4) return ORB_E_NODEVICE;
+    return r ? ORB_E_HIP : ORB_OK;
+}
+
+int orbgpu_unit_pose_stage(const pose_problem* P, const uint8_t* flags, double lambda, int threads, pose_stage* out) {
+    if (!P || !out || !std::isfinite(lambda) || (threads != 256 && threads != 512)) return ORB_E_INVALID;
+    if (P->N < 0 || !P->Tcw || (P->N > 0 && (!flags || !P->has_mp || !P->Xw || !P->obs || !P->inv_sigma2)))
+        return ORB_E_INVALID;
+    const int r = orbgpu::pose_stage_run(P, flags, lambda, threads, out);
+    if (r == -3) return ORB_E_CAPACITY;
+    if (r == -4) return ORB_E_NODEVICE;
     return r ? ORB_E_HIP : ORB_OK;
 }
 

@@ -1,6 +1,7 @@
 // pose_opt.hip -- gfx950 Optimizer::PoseOptimization (PoseEngine, declared in ba.hpp): the edge
 // pack kernel (k_pose_pack), the persistent per-frame optimiser (k_pose_opt) and their host
-// launches.
+// launches; the test-only kernels k_unit_se3 and k_pose_stage (orbgpu_unit_se3,
+// orbgpu_unit_pose_stage), which run the same device functions one stage at a time.
 #include <algorithm>
 #include <cstdlib>
 #include <cstring>
@@ -113,6 +114,72 @@ __device__ __forceinline__ double pose_rho0(const PoseEdgeD& e, double c, bool r
     if (!robust || c <= e.dsqr) return c;
     const double sq = sqrt(c);
     return (2 * sq) * e.delta - e.dsqr;
+}
+
+
+// J, robust weight and the 28 entries (robust chi2, J^T W J upper triangle, -J^T W e) of one edge
+// at pose X, into v[0..28); rb: the edge's robust kernel is set.  J (3 x 6, row-major) and the
+// error e3 are the caller's, so that the stage kernel (k_pose_stage) can report them.
+__device__ __forceinline__ void pose_sys_terms_je(const PoseEdgeD& e, bool rb, const Se3& X, const PoseProbDev& P,
+                                                  double* v, double* J, double* e3) {
+    double p[3];
+    se3_map(X, e.X, p);
+    const SharedDiv dz(p[2]);
+    pose_err_p(e, p, dz, P, e3);
+    const double c = pose_chi2(e, e3);
+    v[0] = pose_rho0(e, c, rb);
+    const double x = p[0], y = p[1], invz = dz.div(1.0), invz_2 = invz * invz;
+    J[0] = ((x * y) * invz_2) * P.fx;
+    J[1] = (-(1 + ((x * x) * invz_2))) * P.fx;
+    J[2] = (y * invz) * P.fx;
+    J[3] = (-invz) * P.fx;
+    J[4] = 0;
+    J[5] = (x * invz_2) * P.fx;
+    J[6] = (1 + ((y * y) * invz_2)) * P.fy;
+    J[7] = (((-x) * y) * invz_2) * P.fy;
+    J[8] = ((-x) * invz) * P.fy;
+    J[9] = 0;
+    J[10] = (-invz) * P.fy;
+    J[11] = (y * invz_2) * P.fy;
+    J[12] = J[0] - ((P.bf * y) * invz_2);
+    J[13] = J[1] + ((P.bf * x) * invz_2);
+    J[14] = J[2];
+    J[15] = J[3];
+    J[16] = 0;
+    J[17] = J[5] - (P.bf * invz_2);
+    // monocular edges: a zero third Jacobian row (and err[2] = 0) makes every
+    // third term +-0, an exact identity on the two-term partial sums (which
+    // start from +0 + t0 and so are never -0): the sums run branch-free
+#pragma unroll
+    for (int j = 12; j < 18; j++) J[j] = e.stereo ? J[j] : 0.0;
+    double r1 = 1.;
+    if (rb && !(c <= e.dsqr)) r1 = e.delta / sqrt(c);
+    const double wgt = rb ? r1 * e.info : e.info;
+    double omr[3];
+#pragma unroll
+    for (int kk = 0; kk < 3; kk++) {
+        omr[kk] = -(e.info * e3[kk]);
+        if (rb) omr[kk] *= r1;
+    }
+#pragma unroll
+    for (int r = 0; r < 6; r++) {
+        double sb = 0;
+#pragma unroll
+        for (int kk = 0; kk < 3; kk++) sb += J[kk * 6 + r] * omr[kk];
+        v[22 + r] = sb;
+#pragma unroll
+        for (int cc = r; cc < 6; cc++) {
+            double hh = 0;
+#pragma unroll
+            for (int kk = 0; kk < 3; kk++) hh += (J[kk * 6 + r] * wgt) * J[kk * 6 + cc];
+            v[1 + r * 6 - (r * (r - 1)) / 2 + (cc - r)] = hh;
+        }
+    }
+}
+__device__ __forceinline__ void pose_sys_terms(const PoseEdgeD& e, bool rb, const Se3& X, const PoseProbDev& P,
+                                               double* v) {
+    double J[18], e3[3];
+    pose_sys_terms_je(e, rb, X, P, v, J, e3);
 }
 
 
@@ -515,11 +582,36 @@ __device__ __forceinline__ bool pose_solve_l(const double* Hs, const double* bs,
     return true;
 }
 
+// k_pose_stage's copy of k_pose_opt's compaction (integer code only; k_pose_opt keeps its own
+// inline: calling this function there changed its register allocation): active edges (bit 0 of fl
+// clear) in edge order into aE, their count into *nA; ends with a barrier
+template <int NT>
+__device__ __forceinline__ void pose_compact(const uint8_t* fl, int ne, uint16_t* aE, int* wsum, int* nA) {
+    constexpr int kPosePer = kPoseMaxEdges / NT;
+    const int tid = threadIdx.x;
+    const int base = tid * kPosePer;
+    int c = 0;
+    for (int j = 0; j < kPosePer; j++) c += (base + j < ne && (fl[base + j] & 1) == 0) ? 1 : 0;
+    int incl = c;   // inclusive scan within the wave
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(incl, o, 64);
+        if ((tid & 63) >= o) incl += t;
+    }
+    if ((tid & 63) == 63) wsum[tid >> 6] = incl;
+    __syncthreads();
+    int off = 0;
+    for (int w = 0; w < (tid >> 6); w++) off += wsum[w];
+    int pos = off + incl - c;
+    for (int j = 0; j < kPosePer; j++)
+        if (base + j < ne && (fl[base + j] & 1) == 0) aE[pos++] = (uint16_t)(base + j);
+    if (tid == blockDim.x - 1) *nA = off + incl;
+    __syncthreads();
+}
+
 template <int NT>
 __global__ void __launch_bounds__(NT) k_pose_opt(PoseProbDev* probs, const PoseEdgeDev* __restrict__ Eall,
                                                  double* errAll, uint8_t* outlAll) {
     ORBGPU_LATENCY_WAVE();
-    constexpr int kPosePer = kPoseMaxEdges / NT;
     PoseProbDev& P = probs[blockIdx.x];
     const int ne = P.ne;
     const PoseEdgeDev* E = Eall + P.e0;
@@ -574,6 +666,7 @@ __global__ void __launch_bounds__(NT) k_pose_opt(PoseProbDev* probs, const PoseE
         }
         // active edges (level 0) in edge order: block prefix over kPosePer edges per thread
         {
+            constexpr int kPosePer = kPoseMaxEdges / NT;
             const int base = tid * kPosePer;
             int c = 0;
             for (int j = 0; j < kPosePer; j++) c += (base + j < ne && (fl[base + j] & 1) == 0) ? 1 : 0;
@@ -597,65 +690,9 @@ __global__ void __launch_bounds__(NT) k_pose_opt(PoseProbDev* probs, const PoseE
         const PoseEdgeD myE = pose_edge_load(E, myIdx, dM, dS);
         if (na > 0) {   // optimize(10); without active edges the vertex is not optimised at all
             ORBGPU_PROF_START;
-            // J, robust weight and the 28 entries (robust chi2, J^T W J upper triangle, -J^T W e)
-            // of active edge i at pose X, into v[0..28)
+            // the 28 entries of active edge i at pose X (pose_sys_terms), into v[0..28)
             auto sys_terms = [&](const PoseEdgeD& e, int i, const Se3& X, double* v) {
-                double p[3];
-                se3_map(X, e.X, p);
-                const SharedDiv dz(p[2]);
-                double e3[3];
-                pose_err_p(e, p, dz, P, e3);
-                const double c = pose_chi2(e, e3);
-                const bool rb = (fl[i] & 2) != 0;
-                v[0] = pose_rho0(e, c, rb);
-                const double x = p[0], y = p[1], invz = dz.div(1.0), invz_2 = invz * invz;
-                double J[18];
-                J[0] = ((x * y) * invz_2) * P.fx;
-                J[1] = (-(1 + ((x * x) * invz_2))) * P.fx;
-                J[2] = (y * invz) * P.fx;
-                J[3] = (-invz) * P.fx;
-                J[4] = 0;
-                J[5] = (x * invz_2) * P.fx;
-                J[6] = (1 + ((y * y) * invz_2)) * P.fy;
-                J[7] = (((-x) * y) * invz_2) * P.fy;
-                J[8] = ((-x) * invz) * P.fy;
-                J[9] = 0;
-                J[10] = (-invz) * P.fy;
-                J[11] = (y * invz_2) * P.fy;
-                J[12] = J[0] - ((P.bf * y) * invz_2);
-                J[13] = J[1] + ((P.bf * x) * invz_2);
-                J[14] = J[2];
-                J[15] = J[3];
-                J[16] = 0;
-                J[17] = J[5] - (P.bf * invz_2);
-                // monocular edges: a zero third Jacobian row (and err[2] = 0) makes every
-                // third term +-0, an exact identity on the two-term partial sums (which
-                // start from +0 + t0 and so are never -0): the sums run branch-free
-#pragma unroll
-                for (int j = 12; j < 18; j++) J[j] = e.stereo ? J[j] : 0.0;
-                double r1 = 1.;
-                if (rb && !(c <= e.dsqr)) r1 = e.delta / sqrt(c);
-                const double wgt = rb ? r1 * e.info : e.info;
-                double omr[3];
-#pragma unroll
-                for (int kk = 0; kk < 3; kk++) {
-                    omr[kk] = -(e.info * e3[kk]);
-                    if (rb) omr[kk] *= r1;
-                }
-#pragma unroll
-                for (int r = 0; r < 6; r++) {
-                    double sb = 0;
-#pragma unroll
-                    for (int kk = 0; kk < 3; kk++) sb += J[kk * 6 + r] * omr[kk];
-                    v[22 + r] = sb;
-#pragma unroll
-                    for (int cc = r; cc < 6; cc++) {
-                        double hh = 0;
-#pragma unroll
-                        for (int kk = 0; kk < 3; kk++) hh += (J[kk * 6 + r] * wgt) * J[kk * 6 + cc];
-                        v[1 + r * 6 - (r * (r - 1)) / 2 + (cc - r)] = hh;
-                    }
-                }
+                pose_sys_terms(e, (fl[i] & 2) != 0, X, P, v);
             };
             // One LM iteration is a system pass at T (skipped when the accepted trial of the
             // previous iteration already evaluated it) followed by trials; a trial is the solves
@@ -863,18 +900,154 @@ __global__ void __launch_bounds__(NT) k_pose_opt(PoseProbDev* probs, const PoseE
     }
     if (P.Tcw_out) {   // pFrame->SetPose(Converter::toCvMat(SE3quat_recov)); mvbOutlier
         if (tid == 0) {
-            double R[9];
-            quat_to_R(T.q, R);
-            float* o = P.Tcw_out;
-            for (int r = 0; r < 3; r++) {
-                for (int c = 0; c < 3; c++) o[r * 4 + c] = (float)R[r * 3 + c];
-                o[r * 4 + 3] = (float)T.t[r];
-            }
-            o[12] = o[13] = o[14] = 0.f;
-            o[15] = 1.f;
+            se3_to_Tcw(T, P.Tcw_out);
             __threadfence_system();   // see the ne < 3 exit above: host-visible before the workgroup ends
         }
         for (int i = tid; i < ne; i += blockDim.x) P.outlier[E[i].meta & 0x7fffffff] = outl[i];
+    }
+}
+
+// ---------------------------------------------------------------- test-only entries' kernels
+// orbgpu_unit_se3: one item per thread through ba_math.hpp's inline functions.  SE3 rows are 7
+// doubles (q xyzw, t).
+__device__ __forceinline__ Se3 se3_row_load(const double* r) {
+    Se3 s;
+    for (int k = 0; k < 4; k++) s.q[k] = r[k];
+    for (int k = 0; k < 3; k++) s.t[k] = r[4 + k];
+    s.pad = 0;
+    return s;
+}
+__device__ __forceinline__ void se3_row_store(const Se3& s, double* r) {
+    for (int k = 0; k < 4; k++) r[k] = s.q[k];
+    for (int k = 0; k < 3; k++) r[4 + k] = s.t[k];
+}
+__global__ void __launch_bounds__(256) k_unit_se3(int op, int n, const void* a, const void* b, void* out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double* A = (const double*)a;
+    const double* B = (const double*)b;
+    double* O = (double*)out;
+    if (op == 0) {
+        Se3 o;
+        se3_exp(A + 6 * (size_t)i, o);
+        se3_row_store(o, O + 7 * (size_t)i);
+    } else if (op == 1) {
+        Se3 o;
+        se3_mul(se3_row_load(A + 7 * (size_t)i), se3_row_load(B + 7 * (size_t)i), o);
+        se3_row_store(o, O + 7 * (size_t)i);
+    } else if (op == 2) {
+        double X[3], p[3];
+        for (int k = 0; k < 3; k++) X[k] = B[3 * (size_t)i + k];
+        se3_map(se3_row_load(A + 7 * (size_t)i), X, p);
+        for (int k = 0; k < 3; k++) O[3 * (size_t)i + k] = p[k];
+    } else if (op == 3) {
+        float T[16];
+        for (int k = 0; k < 16; k++) T[k] = ((const float*)a)[16 * (size_t)i + k];
+        Se3 o;
+        se3_from_Tcw(T, o);
+        se3_row_store(o, O + 7 * (size_t)i);
+    } else {
+        float T[16];
+        se3_to_Tcw(se3_row_load(A + 7 * (size_t)i), T);
+        for (int k = 0; k < 16; k++) ((float*)out)[16 * (size_t)i + k] = T[k];
+    }
+}
+
+// orbgpu_unit_pose_stage: one linearisation at T0 and one LM trial at a given lambda, one
+// workgroup, through k_pose_opt's own device functions.  out (doubles; integers and floats are
+// stored exactly): head = sums 28 | x 6 | T0 7 | T_trial 7 | the trial's sum of rho | scale |
+// nA | ok | Tcw_trial 16, then one row per edge = err 3 | chi2e | rho | J 18 | terms 28 |
+// chi2e_trial | rho_trial | the classification's float chi2 at T_trial | keypoint.  Rows of
+// inactive edges keep what the host put there, except the last two columns.
+constexpr int kStageHead = 68, kStageCols = 55;
+template <int NT>
+__global__ void __launch_bounds__(NT) k_pose_stage(const PoseProbDev* probs, const PoseEdgeDev* __restrict__ E,
+                                                   const uint8_t* flags, double lam, double* out) {
+    const PoseProbDev& P = probs[0];
+    const int ne = P.ne, tid = threadIdx.x;
+    __shared__ uint8_t fl[kPoseMaxEdges];
+    __shared__ uint16_t aE[kPoseMaxEdges];
+    __shared__ double cs[28][kPoseMaxEdges / 64];
+    __shared__ double red[32], sums[28], scr[36], xs[6];
+    __shared__ Se3 T0, Tt;
+    __shared__ int nA, wsum[16];
+    const double dM = (double)(float)sqrt(5.991), dS = (double)(float)sqrt(7.815);
+    double* rows = out + kStageHead;
+    for (int i = tid; i < ne; i += NT) {
+        fl[i] = flags[i];
+        rows[(size_t)i * kStageCols + 54] = (double)(E[i].meta & 0x7fffffff);
+    }
+    if (tid == 0) {
+        T0 = P.T0;
+        for (int j = 0; j < 6; j++) xs[j] = 0.0;   // k_pose_opt's xs at the start of a round
+    }
+    __syncthreads();
+    pose_compact<NT>(fl, ne, aE, wsum, &nA);
+    const int na = nA;
+    const int myIdx = tid < na ? aE[tid] : 0;
+    const PoseEdgeD myE = pose_edge_load(E, myIdx, dM, dS);
+    for (int phase = 0; phase < 2; phase++) {   // 0: the system at T0; 1: the trial's pass at T_trial
+        const Se3& X = phase ? Tt : T0;
+        pose_pass<28>([&](const PoseEdgeD& e, int i, double* v) {
+            double J[18], e3[3];
+            pose_sys_terms_je(e, (fl[i] & 2) != 0, X, P, v, J, e3);
+            double* r = rows + (size_t)i * kStageCols;
+            const double c = pose_chi2(e, e3);
+            if (phase == 0) {
+                for (int k = 0; k < 3; k++) r[k] = e3[k];
+                r[3] = c;
+                r[4] = v[0];
+                for (int k = 0; k < 18; k++) r[5 + k] = J[k];
+                for (int k = 0; k < 28; k++) r[23 + k] = v[k];
+            } else {
+                r[51] = c;
+                r[52] = v[0];
+            }
+        }, na, aE, E, dM, dS, cs, red, myE, myIdx);
+        if (phase == 1) {
+            if (tid == 0) out[48] = red[0];
+            break;
+        }
+        if (tid < 28) {
+            sums[tid] = red[tid];
+            out[tid] = red[tid];
+        }
+        __syncthreads();
+        if (tid < 64) {   // k_pose_opt's candidate 0: solve, step from xs when the solve fails
+            double xn[6], xl[6];
+            const bool ok = pose_solve_l(sums + 1, sums + 22, lam, xn, scr);
+#pragma unroll
+            for (int j = 0; j < 6; j++) xl[j] = ok ? xn[j] : xs[j];
+            Se3 d, r;
+            se3_exp(xl, d);
+            se3_mul(d, T0, r);
+            if (tid == 0) {
+                Tt = r;
+                double sv[6];
+                for (int q = 0; q < 6; q++) {
+                    out[28 + q] = xl[q];
+                    sv[q] = xl[q] * (lam * xl[q] + sums[22 + q]);
+                }
+                out[49] = tree64_local([&](int q) { return sv[q]; }, 6);
+                out[50] = (double)na;
+                out[51] = ok ? 1.0 : 0.0;
+            }
+        }
+        __syncthreads();
+    }
+    // the classification's chi2 (Optimizer.cc:376-426) at the pose of the last pass
+    for (int i = tid; i < ne; i += NT) {
+        const PoseEdgeD e = pose_edge_load(E, i, dM, dS);
+        double e3[3];
+        pose_err(e, Tt, P, e3);
+        rows[(size_t)i * kStageCols + 53] = (double)(float)pose_chi2(e, e3);
+    }
+    if (tid == 0) {
+        se3_row_store(T0, out + 34);
+        se3_row_store(Tt, out + 41);
+        float o[16];
+        se3_to_Tcw(Tt, o);
+        for (int k = 0; k < 16; k++) out[52 + k] = (double)o[k];
     }
 }
 
@@ -890,13 +1063,7 @@ __global__ void __launch_bounds__(kPackThreads) k_pose_pack(PoseProbDev* probs, 
     __shared__ int wsum[kPackThreads / 64], base;
     if (tid == 0) {
         base = 0;
-        double R[9];
-        for (int r = 0; r < 3; r++)
-            for (int c = 0; c < 3; c++) R[r * 3 + c] = (double)P.Tcw[r * 4 + c];
-        quat_from_R(R, P.T0.q);
-        for (int r = 0; r < 3; r++) P.T0.t[r] = (double)P.Tcw[r * 4 + 3];
-        P.T0.pad = 0;
-        se3_normalize(P.T0);
+        se3_from_Tcw(P.Tcw, P.T0);
     }
     __syncthreads();
     for (int c0 = 0; c0 < N; c0 += kPackThreads) {
@@ -1082,6 +1249,22 @@ int PoseEngine::init() {
     return 0;
 }
 
+// Edge creation on the host (Optimizer.cc:268-347): rows with a map point in keypoint order
+static int pose_edges_host(const pose_problem& Q, PoseEdgeDev* he) {
+    int k = 0;
+    for (int i = 0; i < Q.N; i++) {
+        if (!Q.has_mp[i]) continue;
+        PoseEdgeDev& e = he[k++];
+        for (int j = 0; j < 3; j++) {
+            e.Xw[j] = Q.Xw[3 * i + j];
+            e.obs[j] = Q.obs[3 * i + j];
+        }
+        e.info = Q.inv_sigma2[i];
+        e.meta = i | (!(Q.obs[3 * i + 2] < 0) ? (int)0x80000000u : 0);
+    }
+    return k;
+}
+
 // Edge creation (Optimizer.cc:268-347): rows with a map point in keypoint order.
 int PoseEngine::run(int count, const pose_problem* P, float* Tcw_out, uint8_t* const* outlier, int* ninliers) {
     size_t ne = 0;
@@ -1121,16 +1304,7 @@ int PoseEngine::run(int count, const pose_problem* P, float* Tcw_out, uint8_t* c
         pp.e0 = e0;
         host_se3_from_Tcw(Q.Tcw, pp.T0);
         pp.fx = Q.fx; pp.fy = Q.fy; pp.cx = Q.cx; pp.cy = Q.cy; pp.bf = Q.bf;
-        for (int i = 0; i < Q.N; i++) {
-            if (!Q.has_mp[i]) continue;
-            PoseEdgeDev& e = he[e0++];
-            for (int j = 0; j < 3; j++) {
-                e.Xw[j] = Q.Xw[3 * i + j];
-                e.obs[j] = Q.obs[3 * i + j];
-            }
-            e.info = Q.inv_sigma2[i];
-            e.meta = i | (!(Q.obs[3 * i + 2] < 0) ? (int)0x80000000u : 0);
-        }
+        e0 += pose_edges_host(Q, he + e0);
     }
     PoseProbDev* dp = (PoseProbDev*)d;
     ORB_HIP_CHECK(hipMemcpyAsync(d, h, bProb + sizeof(PoseEdgeDev) * ne, hipMemcpyHostToDevice, stream_));
@@ -1166,6 +1340,107 @@ int PoseEngine::run(int count, const pose_problem* P, float* Tcw_out, uint8_t* c
             ninliers[f] = pp.ne - pp.nbad;
         }
     }
+    return 0;
+}
+
+// ---------------------------------------------------------------- test-only entries
+int pose_unit_se3(int op, int n, const void* a, const void* b, void* out) {
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return -4;
+    if (n == 0) return 0;
+    const size_t bA = (op == 0 ? 6 * sizeof(double) : op == 3 ? 16 * sizeof(float) : 7 * sizeof(double)) * (size_t)n;
+    const size_t bB = (op == 1 ? 7 : op == 2 ? 3 : 0) * sizeof(double) * (size_t)n;
+    const size_t bO = (op == 2 ? 3 * sizeof(double) : op == 4 ? 16 * sizeof(float) : 7 * sizeof(double)) * (size_t)n;
+    const auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    char* dm = nullptr;
+    ORB_HIP_CHECK(hipMalloc((void**)&dm, al(bA) + al(bB) + bO));
+    char *dA = dm, *dB = dA + al(bA), *dO = dB + al(bB);
+    int rc = 0;
+    if (hipMemcpy(dA, a, bA, hipMemcpyHostToDevice) != hipSuccess) rc = -2;
+    if (!rc && bB && hipMemcpy(dB, b, bB, hipMemcpyHostToDevice) != hipSuccess) rc = -2;
+    if (!rc) {
+        hipLaunchKernelGGL(k_unit_se3, dim3((n + 255) / 256), dim3(256), 0, 0, op, n, (const void*)dA, (const void*)dB,
+                           (void*)dO);
+        if (hipGetLastError() != hipSuccess || hipMemcpy(out, dO, bO, hipMemcpyDeviceToHost) != hipSuccess) rc = -2;
+    }
+    (void)hipFree(dm);
+    return rc;
+}
+
+int pose_stage_run(const pose_problem* Q, const uint8_t* flags, double lambda, int threads, pose_stage* out) {
+    int nd = 0;
+    if (hipGetDeviceCount(&nd) != hipSuccess || nd <= 0) return -4;
+    int ne = 0;
+    for (int i = 0; i < Q->N; i++) ne += Q->has_mp[i] ? 1 : 0;
+    if (ne > kPoseMaxEdges) return -3;
+    out->ne = ne;
+    out->nA = out->ok = 0;
+    if (ne == 0) return 0;
+    PoseProbDev pp;
+    memset(&pp, 0, sizeof(pp));
+    pp.ne = ne;
+    host_se3_from_Tcw(Q->Tcw, pp.T0);
+    pp.fx = Q->fx; pp.fy = Q->fy; pp.cx = Q->cx; pp.cy = Q->cy; pp.bf = Q->bf;
+    std::vector<PoseEdgeDev> he(ne);
+    pose_edges_host(*Q, he.data());
+    const auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t bP = al(sizeof(pp)), bE = al(sizeof(PoseEdgeDev) * ne), bF = al((size_t)ne);
+    const size_t nOut = kStageHead + (size_t)kStageCols * ne;
+    char* dm = nullptr;
+    ORB_HIP_CHECK(hipMalloc((void**)&dm, bP + bE + bF + sizeof(double) * nOut));
+    double* dO = (double*)(dm + bP + bE + bF);
+    std::vector<double> ho(nOut);
+    int rc = 0;
+    if (hipMemcpy(dm, &pp, sizeof(pp), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dm + bP, he.data(), sizeof(PoseEdgeDev) * ne, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dm + bP + bE, flags, ne, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(dO, 0xff, sizeof(double) * nOut) != hipSuccess)   // NaN wherever the kernel writes nothing
+        rc = -2;
+    if (!rc) {
+        if (threads == kPoseThreadsWide)
+            hipLaunchKernelGGL(k_pose_stage<kPoseThreadsWide>, dim3(1), dim3(kPoseThreadsWide), 0, 0,
+                               (const PoseProbDev*)dm, (const PoseEdgeDev*)(dm + bP), (const uint8_t*)(dm + bP + bE),
+                               lambda, dO);
+        else
+            hipLaunchKernelGGL(k_pose_stage<kPoseThreads>, dim3(1), dim3(kPoseThreads), 0, 0, (const PoseProbDev*)dm,
+                               (const PoseEdgeDev*)(dm + bP), (const uint8_t*)(dm + bP + bE), lambda, dO);
+        if (hipGetLastError() != hipSuccess ||
+            hipMemcpy(ho.data(), dO, sizeof(double) * nOut, hipMemcpyDeviceToHost) != hipSuccess)
+            rc = -2;
+    }
+    (void)hipFree(dm);
+    if (rc) return rc;
+    const double* h = ho.data();
+    out->nA = (int)h[50];
+    out->ok = (int)h[51];
+    out->chi2_trial = h[48];
+    out->scale = h[49];
+    const auto put = [&](double* dst, int col, int w) {
+        if (!dst) return;
+        for (int i = 0; i < ne; i++)
+            for (int k = 0; k < w; k++) dst[(size_t)i * w + k] = h[kStageHead + (size_t)i * kStageCols + col + k];
+    };
+    put(out->err, 0, 3);
+    put(out->chi2e, 3, 1);
+    put(out->rho, 4, 1);
+    put(out->J, 5, 18);
+    put(out->terms, 23, 28);
+    put(out->chi2e_trial, 51, 1);
+    put(out->rho_trial, 52, 1);
+    for (int i = 0; i < ne; i++) {
+        const double* r = h + kStageHead + (size_t)i * kStageCols;
+        if (out->chi2_class) out->chi2_class[i] = (float)r[53];
+        if (out->keypoint) out->keypoint[i] = (int32_t)r[54];
+    }
+    const auto head = [&](double* dst, int o, int w) {
+        if (dst) memcpy(dst, h + o, sizeof(double) * w);
+    };
+    head(out->sums, 0, 28);
+    head(out->x, 28, 6);
+    head(out->T0, 34, 7);
+    head(out->T_trial, 41, 7);
+    if (out->Tcw_trial)
+        for (int k = 0; k < 16; k++) out->Tcw_trial[k] = (float)h[52 + k];
     return 0;
 }
 

@@ -1568,6 +1568,40 @@ int orbgpu_unit_essgraph_stage(const essgraph_problem* P, double lambda, essgrap
 /* Test knob: the pose graph's dense single-workgroup solver takes systems of at most `rows` rows
  * (default and maximum 144); 0 sends every system to the block-sparse solver.  Process-wide. */
 int orbgpu_unit_set_ess_dense_max(int rows);
+/* The SE3 arithmetic PoseOptimization and the BA engines share (csrc/ba_math.hpp: g2o SE3Quat),
+ * one thread per item through the kernels' own inline functions.  No reference counterpart.  SE3
+ * rows are 7 doubles (q xyzw, t).  op 0: exp, a n x 6 doubles (omega, upsilon) -> out n x 7;
+ * 1: a * b -> n x 7; 2: a.map(b), b n x 3 doubles -> n x 3 doubles; 3: Converter::toSE3Quat,
+ * a n x 16 FLOATS (row-major Tcw) -> n x 7; 4: the pose write-back, a n x 7 -> out n x 16 FLOATS.
+ * b may be NULL where unused. */
+int orbgpu_unit_se3(int op, int n, const void* a, const void* b, void* out);
+/* One linearisation and one LM trial of Optimizer_PoseOptimization at a given lambda, in one
+ * workgroup of `threads` (256 or 512) threads through k_pose_opt's own device functions.  No
+ * reference counterpart.  The estimate is toSE3Quat(P->Tcw); edges are the rows with has_mp, in
+ * keypoint order; flags holds one byte per edge (bit 0: inactive, bit 1: robust kernel set).
+ * Every pointer may be NULL (skipped).  Per-edge outputs of inactive edges are NaN, except
+ * keypoint and chi2_class.  At most 8192 edges (ORB_E_CAPACITY). */
+typedef struct pose_stage {
+    int ne, nA;           /* out: edges, active edges */
+    int ok;               /* out: the solve succeeded (0: x is the untouched zero step) */
+    int32_t* keypoint;    /* ne: edge -> keypoint index */
+    double* T0;           /* 7 */
+    double* err;          /* ne x 3 (row 3 of a monocular edge is 0) */
+    double* chi2e;        /* ne */
+    double* rho;          /* ne: robust chi2 */
+    double* J;            /* ne x 18: [row][column], columns (omega, upsilon) */
+    double* terms;        /* ne x 28: rho | H upper triangle by rows (21) | b (6) */
+    double* sums;         /* 28: the canonical sums of terms over the active edges */
+    double* x;            /* 6 */
+    double* T_trial;      /* 7: exp(x) * T0 */
+    double* chi2e_trial;  /* ne */
+    double* rho_trial;    /* ne */
+    float* chi2_class;    /* ne: the outlier classification's float chi2 at T_trial */
+    float* Tcw_trial;     /* 16: T_trial through the pose write-back */
+    double chi2_trial;    /* out: the canonical sum of rho_trial */
+    double scale;         /* out: computeScale without its 1e-3 */
+} pose_stage;
+int orbgpu_unit_pose_stage(const pose_problem* P, const uint8_t* flags, double lambda, int threads, pose_stage* out);
 /* Test knob: a KeyFrameDatabase created from now on starts with room for `slots` keyframes and
  * `entries` BowVector entries (defaults 1024 and 1 << 20; both double when full, and the entry
  * pool is compacted when its holes exceed its live entries); 0 restores a default.  Returns 1 on

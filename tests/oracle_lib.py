@@ -685,6 +685,7 @@ def oracle_pose_optimization(pr):
     tr = _BATrace()
     n = L.ora_pose_optimization(C.byref(P), ptr(T), ptr(outl), C.byref(tr))
     return dict(Tcw=T.reshape(4, 4), outlier=outl, inliers=n, solve_chi2=np.array(tr.solve_chi2[:tr.n_solves]),
+                solve_ini_chi2=np.array(tr.solve_ini_chi2[:tr.n_solves]),
                 trial_chi2=np.array(tr.trial_chi2[:tr.n_trials]), trial_lambda=np.array(tr.trial_lambda[:tr.n_trials]))
 
 

@@ -47,6 +47,33 @@ def test_pose_edge_cases(gpu, kw):
     _check(pr, n, T, outl)
 
 
+def test_pose_points_behind_the_camera(gpu):
+    """about 10 % of the points at negative depth, every number finite: SharedDiv and the Jacobian at
+    p_z < 0, bit-identical to the oracle (which runs 18 solves and 43 trials and moves the pose)"""
+    from c_orb_slam_amd import PoseOptimization
+    from pose_stage_cases import negative_depth_frame
+    pr = negative_depth_frame()
+    assert 20 <= pr["behind"].sum() <= 40
+    n, T, outl = PoseOptimization(pr)
+    o = _check(pr, n, T, outl)
+    assert np.all(np.isfinite(o["solve_chi2"])) and not np.array_equal(o["Tcw"], pr["Tcw"])
+    assert (len(o["solve_chi2"]), len(o["trial_chi2"]), o["inliers"]) == (18, 43, 235)
+
+
+def test_pose_degenerate_depths(gpu):
+    """p_z = 0 exactly, p_z = -3 and Xw = (0, 0, 0) in one frame at the identity pose: the plain-division
+    arm of SharedDiv, a non-finite chi2 and H, and 40 solves on a NaN system.  The oracle returns 64
+    inliers, a NaN chi2 trace and the start pose unchanged; the kernel's loops are bounded by
+    kit < 10 and qmax < 10, so the call returns, bit-identical."""
+    from c_orb_slam_amd import PoseOptimization
+    from pose_stage_cases import degenerate_depth_frame
+    pr = degenerate_depth_frame()
+    n, T, outl = PoseOptimization(pr)
+    o = _check(pr, n, T, outl)
+    assert o["inliers"] == 64 and len(o["solve_chi2"]) == 40 and np.all(np.isnan(o["solve_chi2"]))
+    assert np.array_equal(o["Tcw"], pr["Tcw"]) and np.array_equal(T, np.eye(4, dtype=np.float32))
+
+
 def test_pose_too_few_correspondences(gpu):
     from c_orb_slam_amd import PoseOptimization
     pr = pose_problem(3, N=30)
