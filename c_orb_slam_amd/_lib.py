@@ -17,6 +17,7 @@ LIB_PATH = Path(os.environ["ORBGPU_LIB"]) if os.environ.get("ORBGPU_LIB") else P
 HEADER = ROOT / "include" / "orbslam_gpu.h"
 
 ORB_OK, ORB_E_INVALID, ORB_E_HIP, ORB_E_CAPACITY, ORB_E_NODEVICE = 0, -1, -2, -3, -4
+ORB_REMAP_SLOTS = 4
 _ERR = {ORB_E_INVALID: "ORB_E_INVALID", ORB_E_HIP: "ORB_E_HIP", ORB_E_CAPACITY: "ORB_E_CAPACITY",
         ORB_E_NODEVICE: "ORB_E_NODEVICE"}
 
@@ -138,6 +139,8 @@ def lib():
     L.ORBextractor_extract_batch.argtypes = [vp, vp, i32, i32, i32, i32, sz, i32, vp, vp, i32, i32, vp]
     L.ORBextractor_extract_images.argtypes = [vp, vp, i32, i32, i32, i32, vp, vp, i32, i32, vp]
     L.ORBextractor_cvtColor_batch.argtypes = [vp, vp, i32, i32, i32, i32, i32, i32, sz, i32, vp, i32, sz]
+    L.ORBextractor_set_remap.argtypes = [vp, i32, vp, vp, i32, i32, sz, i32]
+    L.ORBextractor_remap_batch.argtypes = [vp, vp, i32, i32, i32, i32, sz, i32, i32, i32, vp, i32, sz]
     L.ORBextractor_get_level.argtypes = [vp, i32, i32, vp, i32, P(i32), P(i32)]
     L.ORBextractor_get_blurred_level.argtypes = [vp, i32, i32, vp, i32, P(i32), P(i32)]
     L.ORBextractor_get_levels.argtypes = [vp, P(i32), P(f32)]

@@ -1,6 +1,7 @@
-// capi_frame_input.cpp -- extern "C" ORBextractor_cvtColor_batch and Frame_ComputeStereoFromRGBD[_batch]
-// (include/orbslam_gpu.h): the cvtColor of Tracking::GrabImageStereo / GrabImageRGBD /
-// GrabImageMonocular, and Frame::ComputeStereoFromRGBD with GrabImageRGBD's depth conversion.
+// capi_frame_input.cpp -- extern "C" ORBextractor_cvtColor_batch, ORBextractor_set_remap / _remap_batch and
+// Frame_ComputeStereoFromRGBD[_batch] (include/orbslam_gpu.h): the cvtColor of Tracking::GrabImageStereo /
+// GrabImageRGBD / GrabImageMonocular, stereo_euroc.cc's cv::remap rectification, and
+// Frame::ComputeStereoFromRGBD with GrabImageRGBD's depth conversion.
 #include <cmath>
 #include <cstring>
 #include <vector>
@@ -69,6 +70,45 @@ int ORBextractor_cvtColor_batch(ORBextractor_h h, const uint8_t* src, int batch,
     if (batch > 1 && (img_stride < one || gray_stride < gone)) return ORB_E_INVALID;
     const int rc = h->ex->cvt_color(src, batch, width, height, channels, rgb != 0, step, img_stride,
                                     src_on_device != 0, gray_dev, gray_step, gray_stride);
+    return rc == 0 ? ORB_OK : (rc == -2 ? ORB_E_HIP : ORB_E_INVALID);
+}
+
+int ORBextractor_set_remap(ORBextractor_h h, int slot, const float* map1, const float* map2, int dst_width,
+                           int dst_height, size_t map_step, int maps_on_device) {
+    if (!h || slot < 0 || slot >= ORB_REMAP_SLOTS) return ORB_E_INVALID;
+    if (map1 || map2) {   // both null clears the slot
+        if (!map1 || !map2 || dst_width < 1 || dst_height < 1 || dst_width > orbgpu::kRemapMaxDim ||
+            dst_height > orbgpu::kRemapMaxDim || map_step < 4 * (size_t)dst_width)
+            return ORB_E_INVALID;
+    }
+    const int rc = h->ex->set_remap(slot, map1, map2, dst_width, dst_height, map_step, maps_on_device != 0);
+    return rc == 0 ? ORB_OK : (rc == -2 ? ORB_E_HIP : ORB_E_INVALID);
+}
+
+int ORBextractor_remap_batch(ORBextractor_h h, const uint8_t* src, int batch, int src_width, int src_height, int step,
+                             size_t img_stride, int src_on_device, int slot0, int slot_period, uint8_t* dst_dev,
+                             int dst_step, size_t dst_stride) {
+    if (!h || batch < 0) return ORB_E_INVALID;
+    if (batch == 0) return ORB_OK;
+    if (!src || !dst_dev || batch > orbgpu::kCvtMaxBatch || src_width < 1 || src_height < 1 ||
+        src_width > orbgpu::kRemapMaxDim || src_height > orbgpu::kRemapMaxDim || step < src_width)
+        return ORB_E_INVALID;
+    if (slot_period < 1 || slot0 < 0 || slot0 + slot_period > ORB_REMAP_SLOTS) return ORB_E_INVALID;
+    // every slot an image of the batch goes through is set, and all are of one size
+    int dw = 0, dh = 0;
+    for (int j = 0; j < slot_period && j < batch; j++) {
+        int w = 0, hh = 0;
+        if (!h->ex->remap_size(slot0 + j, &w, &hh) || (j > 0 && (w != dw || hh != dh))) return ORB_E_INVALID;
+        dw = w;
+        dh = hh;
+    }
+    if (dst_step < dw) return ORB_E_INVALID;
+    // images of a batch may not overlap
+    const size_t one = (size_t)step * (size_t)(src_height - 1) + (size_t)src_width;
+    const size_t done = (size_t)dst_step * (size_t)(dh - 1) + (size_t)dw;
+    if (batch > 1 && (img_stride < one || dst_stride < done)) return ORB_E_INVALID;
+    const int rc = h->ex->remap(src, batch, src_width, src_height, step, img_stride, src_on_device != 0, slot0,
+                                slot_period, dst_dev, dst_step, dst_stride);
     return rc == 0 ? ORB_OK : (rc == -2 ? ORB_E_HIP : ORB_E_INVALID);
 }
 

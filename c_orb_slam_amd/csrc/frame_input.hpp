@@ -20,6 +20,14 @@ int cvt_gray_launch(const uint8_t* src, int batch, int width, int height, int ch
 constexpr long long kCvtMaxQuads = 256LL * 0x7fffffff;
 constexpr int kCvtMaxBatch = 65535;
 
+// cv::remap(src, dst, map1, map2, INTER_LINEAR) (Extractor::set_remap / remap): largest source and
+// destination side, the record value of a pixel whose taps are all outside any source, and the
+// images of one slot a thread makes from the record it holds (4 measured fastest of 1, 2, 4, 8 and
+// 64 at 128 images of 752x480; ORBGPU_REMAP_IPT overrides it for that measurement)
+constexpr int kRemapMaxDim = 16384;
+constexpr uint32_t kRemapOutside = 0xFFFFu;
+constexpr int kRemapImagesPerThread = 4;
+
 constexpr int kDepthU16 = 0, kDepthF32 = 1;   // ORB_DEPTH_U16 / ORB_DEPTH_F32
 
 // Frame::ComputeStereoFromRGBD of one frame; every pointer is device memory

@@ -1080,6 +1080,7 @@ Extractor::Extractor(int nfeatures, float scaleFactor, int nlevels, int iniTh, i
 Extractor::~Extractor() { release(); }
 
 void Extractor::release() {
+    release_remap();
     auto F = [](void* p) { if (p) (void)hipFree(p); };
     F(d_in_); F(d_pyr_); F(d_blur_); F(d_slots_); F(d_counts_); F(d_cells_); F(d_tiles_); F(d_work_); F(d_groups_);
     F(d_lcb_); F(d_packed_); F(d_hdr_); F(d_sel_); F(d_levels_); F(d_tabs_);

@@ -109,6 +109,15 @@ public:
     // host `src` goes through the pinned staging block extract() uses; `gray` is device memory
     int cvt_color(const uint8_t* src, int B, int W, int H, int channels, int rgb, int step, size_t img_stride,
                   bool src_on_device, uint8_t* gray, int gray_step, size_t gray_stride);
+    // The EuRoC stereo driver's cv::remap rectification (frame_input.hip).  set_remap quantises the
+    // two float maps of a camera into the slot's packed records (a kernel on stream(); both null:
+    // the slot is cleared); what the slot held is freed once the stream has passed it.  remap warps
+    // B 8-bit images, image b through slot slot0 + b % period, into device images of the slots' size.
+    int set_remap(int slot, const float* map1, const float* map2, int W, int H, size_t map_step, bool on_device);
+    int remap(const uint8_t* src, int B, int sw, int sh, int step, size_t img_stride, bool src_on_device, int slot0,
+              int period, uint8_t* dst, int dst_step, size_t dst_stride);
+    // size of the maps `slot` holds; false: unset
+    bool remap_size(int slot, int* w, int* h) const;
     int get_level(int index, int level, uint8_t* dst, int dst_step, int* w, int* h);
     int get_blurred(int index, int level, uint8_t* dst, int dst_step, int* w, int* h);
     int timings(float* ms6);
@@ -141,6 +150,24 @@ private:
     static void gaussian_taps(int taps[7]);
     int setup_geometry(int W, int H);
     void release();
+    // host images into d_in_ through the pinned block h_in_ (one H2D copy on stream_); *dev = d_in_
+    int stage_host(const uint8_t* src, size_t need, const uint8_t** dev);
+    // cv::remap: per slot three uint16 planes (ix + 1, iy + 1, fx | fy << 5) of pitch x h records
+    struct RemapSlot {
+        uint16_t* rec = nullptr;
+        int w = 0, h = 0, pitch = 0;
+    };
+    RemapSlot remap_[ORB_REMAP_SLOTS];
+    // storage a queued kernel may still read: freed when its event (recorded on stream_) is done
+    struct Retired {
+        void* p;
+        bool host;
+        hipEvent_t ev;
+    };
+    std::vector<Retired> retired_;
+    int retire(void* p, bool host);
+    void sweep_retired(bool wait);
+    void release_remap();
 
     int nfeatures_;
     double scaleFactorD_;

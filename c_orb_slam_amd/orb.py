@@ -29,6 +29,7 @@ class ORBextractor:
         self.nfeatures, self.nlevels = int(nfeatures), int(nlevels)
         self.max_batch = int(max_batch)
         self._cap = max(64, 2 * int(nfeatures) + 64)
+        self._remap_sizes = {}   # slot -> (H, W) of the maps set_remap gave it
 
     def close(self):
         if getattr(self, "_h", None):
@@ -113,6 +114,75 @@ class ORBextractor:
                 self._cap *= 2
                 continue
             check(rc, "ORBextractor_extract_batch(grey on device)")
+            n = int(n[0])
+            return kps[:n].copy(), (desc[:n].copy() if n else None)
+
+    def set_remap(self, slot, map1, map2):
+        """The two CV_32FC1 maps of cv::initUndistortRectifyMap(..., CV_32F, map1, map2) of one camera
+        (stereo_euroc.cc: M1l / M2l, M1r / M2r) as H x W float32 numpy arrays, kept in `slot` of this
+        extractor; both None clears the slot.  Row strides are kept."""
+        if map1 is None and map2 is None:
+            check(self._L.ORBextractor_set_remap(self._h, int(slot), None, None, 0, 0, 0, 0), "ORBextractor_set_remap")
+            self._remap_sizes.pop(int(slot), None)
+            return
+        m1, m2 = np.asarray(map1), np.asarray(map2)
+        if m1.ndim != 2 or m1.shape != m2.shape or m1.dtype != np.float32 or m2.dtype != np.float32:
+            raise ValueError("set_remap takes two H x W float32 maps of equal size")
+        if m1.strides[1] != 4 or m1.strides[0] < 4 * m1.shape[1]:
+            m1 = np.ascontiguousarray(m1)
+        if m2.strides != m1.strides:
+            m2 = np.ascontiguousarray(m2)
+            m1 = np.ascontiguousarray(m1)
+        H, W = m1.shape
+        check(self._L.ORBextractor_set_remap(self._h, int(slot), ptr(m1), ptr(m2), W, H, m1.strides[0], 0),
+              "ORBextractor_set_remap")
+        self._remap_sizes[int(slot)] = (H, W)
+
+    def set_remap_device(self, slot, map1_ptr, map2_ptr, W, H, map_step):
+        """set_remap from device-resident maps (raw device addresses, rows map_step bytes apart): they
+        are read by a kernel on this extractor's stream and must stay valid until it has run."""
+        check(self._L.ORBextractor_set_remap(self._h, int(slot), C.c_void_p(map1_ptr), C.c_void_p(map2_ptr), int(W),
+                                             int(H), int(map_step), 1), "ORBextractor_set_remap(device)")
+        self._remap_sizes[int(slot)] = (int(H), int(W))
+
+    def remap_device(self, src_ptr, B, W, H, step, img_stride, slot0, slot_period, d_dst_ptr, dst_step, dst_stride,
+                     src_on_device=True):
+        """cv::remap(src, dst, map1, map2, cv::INTER_LINEAR) of stereo_euroc.cc for B 8-bit W x H images,
+        image b through slot slot0 + b % slot_period, enqueued on this extractor's stream: raw pointers
+        as extract_device takes them (src a device address, or a host address with
+        src_on_device=False); the rectified images (of the slots' size) are always device memory, so
+        extract_device on this extractor can follow without a wait."""
+        check(self._L.ORBextractor_remap_batch(self._h, C.c_void_p(src_ptr), int(B), int(W), int(H), int(step),
+                                               int(img_stride), int(bool(src_on_device)), int(slot0),
+                                               int(slot_period), C.c_void_p(d_dst_ptr), int(dst_step),
+                                               int(dst_stride)), "ORBextractor_remap_batch")
+
+    def extract_rectified(self, image, slot=0):
+        """stereo_euroc.cc on one raw image: cv::remap through `slot` (H x W host array) on the GPU, then
+        operator() on the rectified image it leaves in HBM.  Returns what __call__ returns."""
+        import torch
+        img = np.asarray(image)
+        if img.ndim != 2 or img.dtype != np.uint8 or img.size == 0:
+            raise ValueError("extract_rectified takes a non-empty H x W uint8 image")
+        img = np.ascontiguousarray(img)
+        sz = self._remap_sizes.get(int(slot))
+        if sz is None:
+            raise ValueError(f"remap slot {slot} is not set")
+        H, W = img.shape
+        dh, dw = sz
+        rect = torch.empty((dh, dw), dtype=torch.uint8, device=torch.device("cuda", torch.cuda.current_device()))
+        self.remap_device(img.ctypes.data, 1, W, H, img.strides[0], img.strides[0] * H, slot, 1, rect.data_ptr(),
+                          dw, dw * dh, src_on_device=False)
+        while True:
+            kps = np.zeros(self._cap, KP_DTYPE)
+            desc = np.zeros((self._cap, 32), np.uint8)
+            n = np.zeros(1, np.int32)
+            rc = self._L.ORBextractor_extract_batch(self._h, C.c_void_p(rect.data_ptr()), 1, dw, dh, dw, dw * dh, 1,
+                                                    ptr(kps), ptr(desc), self._cap, 0, ptr(n))
+            if rc == ORB_E_CAPACITY:
+                self._cap *= 2
+                continue
+            check(rc, "ORBextractor_extract_batch(rectified on device)")
             n = int(n[0])
             return kps[:n].copy(), (desc[:n].copy() if n else None)
 

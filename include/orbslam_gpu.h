@@ -106,6 +106,70 @@ int ORBextractor_cvtColor_batch(ORBextractor_h h, const uint8_t* src, int batch,
                                 int channels, int rgb, int step, size_t img_stride, int src_on_device,
                                 uint8_t* gray_dev, int gray_step, size_t gray_stride);
 
+/* Stereo rectification of Examples/Stereo/stereo_euroc.cc: after
+ *   cv::initUndistortRectifyMap(K_l, D_l, R_l, P_l(3x3), size, CV_32F, M1l, M2l)      (once)
+ * every frame goes through cv::remap(imLeft, imLeftRect, M1l, M2l, cv::INTER_LINEAR) (and the right
+ * image through M1r, M2r) before TrackStereo.  The maps are taken as the driver computed them:
+ * initUndistortRectifyMap itself stays with OpenCV (once per camera, in double, its bits depend on
+ * the OpenCV build).
+ *
+ * The specification is OpenCV 3.2 imgwarp.cpp, RemapInvoker's float-map branch and then
+ * remapBilinear<FixedPtCast<int, uchar, 15>, ..., short>.  For a destination pixel with map values
+ * mx, my (float32):
+ *   1. sx = cvRound(mx * 32), sy = cvRound(my * 32): a float32 multiply (exact, 32 is a power of
+ *      two), rounded to nearest, ties to even (rintf; _mm_cvtps_epi32 in the SIMD path);
+ *   2. ix = sx >> 5, iy = sy >> 5 (arithmetic: a floor), fx = sx & 31, fy = sy & 31.  OpenCV
+ *      saturates ix, iy to short: with sizes up to 16384 a saturated value is outside the image
+ *      either way.  A non-finite map value, or one with |m * 32| >= 2^30, counts as far outside and
+ *      the pixel is 0 (a stated simplification of an int conversion that x86 leaves at INT_MIN; the
+ *      byte is the same);
+ *   3. the taps S(iy, ix), S(iy, ix+1), S(iy+1, ix), S(iy+1, ix+1): a tap inside
+ *      [0, src_width) x [0, src_height) reads the source, a tap outside is 0 and is never addressed
+ *      (OpenCV's inlier, fully-outside and BORDER_CONSTANT straddling branches in one rule);
+ *   4. w00 = 32(32-fx)(32-fy), w01 = 32 fx (32-fy), w10 = 32(32-fx) fy, w11 = 32 fx fy, in integers;
+ *      they sum to 32768;
+ *   5. dst = (S00 w00 + S01 w01 + S10 w10 + S11 w11 + 16384) >> 15, at most 255.
+ * The closed form of step 4 is OpenCV's table: initInterTab2D stores
+ * saturate_cast<short>(vy * vx * 32768) with vx in {1 - fx/32, fx/32} and vy likewise, products of
+ * 5-bit ratios that are exact in float and after scaling.  The one value a short cannot hold is
+ * 32768 at fx = fy = 0; there OpenCV stores 32767 and its sum fix-up adds the missing 1 to another
+ * entry of the 2 x 2 block, and (S00*32767 + S*1 + 16384) >> 15 == S00 for all bytes S00, S, so the
+ * output byte is the same.  "Parity unpinned" at this OpenCV call site, as cvtColor:
+ * the restatement is tests/remap_ref.py.  One channel, INTER_LINEAR, BORDER_CONSTANT with value 0:
+ * the only form the reference calls. */
+#define ORB_REMAP_SLOTS 4
+
+/* The two CV_32FC1 maps of cv::initUndistortRectifyMap(..., CV_32F, map1, map2) as the driver
+ * computed them (stereo_euroc.cc: M1l/M2l, M1r/M2r), kept on the handle in `slot`
+ * (0 .. ORB_REMAP_SLOTS-1).  dst_width x dst_height (1 .. 16384 each) is the size of the maps and of
+ * every image remapped through the slot; rows of both maps are map_step bytes apart
+ * (>= 4*dst_width); no alignment is required.  maps_on_device != 0: device pointers, read by a
+ * kernel enqueued on ORBextractor_stream(h) (they must stay valid until the stream has passed it;
+ * host maps are copied before the call returns).  The maps are quantised once, here (steps 1 and
+ * 2), into 6 bytes per pixel.  Replaces what the slot held: a remap through the slot that is
+ * still queued sees the old maps.  map1 == NULL && map2 == NULL clears the slot. */
+int ORBextractor_set_remap(ORBextractor_h h, int slot, const float* map1, const float* map2,
+                           int dst_width, int dst_height, size_t map_step, int maps_on_device);
+
+/* cv::remap(src, dst, map1, map2, cv::INTER_LINEAR) with its defaults (BORDER_CONSTANT, value 0)
+ * for `batch` 8-bit 1-channel images of src_width x src_height (1 .. 16384 each), image b at
+ * src + b*img_stride, rows `step` >= src_width bytes apart, host (staged like
+ * ORBextractor_cvtColor_batch's source) or device.  Image b goes through slot
+ * slot0 + b % slot_period, so slot_period 1 means one camera and slot_period 2 means left / right
+ * interleaved.  Every slot used must be set and of equal size.  The result is always a device
+ * image of the slot's size: image b at dst_dev + b*dst_stride, rows dst_step >= dst_width bytes
+ * apart.  No alignment is required of any pointer or pitch; the images of a batch may not overlap
+ * (img_stride and dst_stride are checked when batch > 1); batch <= 65535, and a batch of 0 returns
+ * ORB_OK and does nothing.  Null pointers, an unset slot, slots of unequal size, slot_period < 1,
+ * slot0 < 0 or slot0 + slot_period > ORB_REMAP_SLOTS and a pitch below a row's bytes return
+ * ORB_E_INVALID before any device work.  Enqueued on ORBextractor_stream(h), does not wait: a
+ * following ORBextractor_extract_batch(h, dst_dev, ..., imgs_on_device = 1, ...) on the same
+ * handle sees the rectified images. */
+int ORBextractor_remap_batch(ORBextractor_h h, const uint8_t* src, int batch, int src_width,
+                             int src_height, int step, size_t img_stride, int src_on_device,
+                             int slot0, int slot_period, uint8_t* dst_dev, int dst_step,
+                             size_t dst_stride);
+
 /* mvImagePyramid[level] (ORBextractor.h:85) of image `index` of the last call,
  * copied to host WITH its 19-px REFLECT_101 border (Frame.cc:573-580 reads it).
  * dst must hold (w+38)*(h+38) bytes at stride dst_step; *w,*h = unpadded dims. */
