@@ -306,6 +306,8 @@ def lib():
     L.LocalMapping_MapPointCulling.argtypes = [vp, vp]
     L.LoopClosing_CorrectLoop.argtypes = [vp, vp, vp]
     L.LoopClosing_ApplyGlobalBA.argtypes = [vp, vp, vp]
+    L.LocalMapping_SearchInNeighbors.argtypes = [vp, vp, vp]
+    L.LocalMapping_SearchInNeighbors_last_timings.argtypes = [vp, vp]
     L.orbgpu_unit_set_map_initial_capacity.argtypes = [i32, i32, i32]
     L.orbgpu_unit_set_map_chunk.argtypes = [i32]
     L.orbgpu_unit_set_map_lds_slots.argtypes = [i32]
@@ -436,6 +438,17 @@ class orb_gbaapply(C.Structure):
                 ("mp_in_gba", C.c_void_p), ("TcwBefGBA", C.c_void_p), ("kf_done", C.c_void_p),
                 ("n_kf_propagated", C.c_int32), ("n_mp_gba", C.c_int32), ("n_mp_moved", C.c_int32),
                 ("depth", C.c_int32)]
+
+
+class orb_searchneigh(C.Structure):
+    _fields_ = [("cur_kf", C.c_int32), ("cur", C.POINTER(orb_frame)), ("ntargets", C.c_int),
+                ("target_id", C.c_void_p), ("target", C.POINTER(orb_frame)), ("th", C.c_float),
+                ("logScaleFactor", C.c_float), ("n_kf_rows", C.c_int), ("kf_desc", C.c_void_p), ("Ow", C.c_void_p),
+                ("nlevels", C.c_int), ("scale_factors", C.c_void_p), ("n", C.c_int), ("pos", C.c_void_p),
+                ("desc", C.c_void_p), ("normal", C.c_void_p), ("max_dist", C.c_void_p), ("min_dist", C.c_void_p),
+                ("bad", C.c_void_p), ("ref_kf", C.c_void_p), ("apply", C.c_int), ("cap_ops", C.c_int),
+                ("cap_updated", C.c_int), ("nfused", C.c_void_p), ("ops", C.c_void_p), ("updated", C.c_void_p),
+                ("n_ops", C.c_int32), ("n_updated", C.c_int32), ("n_ref_missing", C.c_int32)]
 
 
 class pose_frame(C.Structure):

@@ -2,6 +2,7 @@
 #pragma once
 #include <mutex>
 
+#include "fuse.hpp"
 #include "map.hpp"
 #include "orb_extract.hpp"
 #include "orb_match.hpp"
@@ -17,4 +18,5 @@ struct ORBmatcher_t {
 struct Map_t {
     orbgpu::Map map;
     std::mutex mu;   // stands for Map::mMutexMap, KeyFrame::mMutexFeatures / mMutexConnections
+    orbgpu::FuseWork fuse;   // LocalMapping_SearchInNeighbors' device buffers (capi_fuse.cpp)
 };

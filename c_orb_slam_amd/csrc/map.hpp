@@ -165,6 +165,18 @@ public:
     const std::vector<int32_t>& children(int slot) const { return nb_[slot].children; }
     // a keyframe that is its own descendant over the live keyframes' children lists
     bool children_cyclic() const;
+    // the host mirror of one live row, read only (capi_fuse.cpp works on a copy of what it changes)
+    bool slot_live(int slot) const { return slots_[slot].live != 0; }
+    const int32_t* row_mp(int slot) const { return h_mp_.data() + slots_[slot].off; }
+    const uint8_t* row_obs(int slot) const { return h_obs_.data() + slots_[slot].off; }
+    const uint8_t* row_oct(int slot) const { return h_oct_.data() + slots_[slot].off; }
+    const uint8_t* row_flags(int slot) const { return h_flags_.data() + slots_[slot].off; }
+    // the cells (slot * kMapMaxRow + index) that hold map point `mp`, in no order; null: none
+    const std::vector<uint32_t>* cells_of(int32_t mp) const {
+        auto it = held_.find(mp);
+        return it == held_.end() ? nullptr : &it->second;
+    }
+    bool timing_on() const { return timing_; }
 
     void set_chunk(int frames) { chunk_ = frames; }
     void set_lds_slots(int n) { lds_slots_ = n; }

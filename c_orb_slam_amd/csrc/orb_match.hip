@@ -1108,6 +1108,14 @@ int Matcher::area_candidates(const SearchDev& frame, const AreaQuery* d_q, int n
     return 0;
 }
 
+int Matcher::build_grids(SearchDev* d_probs, int np, int maxN) {
+    if (np <= 0) return 0;
+    if (maxN > kMaxFrameKeys || maxN < 0) return -1;
+    hipLaunchKernelGGL(k_build_grid, dim3(np), dim3(256), grid_lds_bytes(maxN), stream_, d_probs, 0);
+    ORB_HIP_CHECK(hipGetLastError());
+    return 0;
+}
+
 // --------------------------------------------------------------------- host
 Matcher::~Matcher() {
     for (int i = 0; i < 16; i++)

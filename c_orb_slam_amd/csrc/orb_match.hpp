@@ -160,6 +160,9 @@ public:
     // (its cur frame: device keysUn/desc + grid geometry), CSR in reference order, to host.
     int area_candidates(const SearchDev& frame, const AreaQuery* d_q, int nq, const uint8_t* d_qdesc,
                         std::vector<int>& off, std::vector<int2>& cand);
+    // Frame::mGrid of `np` frames (d_probs[i].cur with gridStart / gridIdx set, all device memory)
+    // in one launch on stream(): every keypoint is placed, cells list their keypoints in index order
+    int build_grids(SearchDev* d_probs, int np, int maxN);
     // device arena for host-pointer mode: reserve() resets it, alloc() carves it
     int arena_reserve(size_t bytes);
     void* arena_alloc(size_t bytes);

@@ -11,7 +11,16 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import ORB_E_CAPACITY, OrbGpuError, check, lib, orb_connections, orb_kfcull, orb_pointcull, ptr
+from ._lib import (ORB_E_CAPACITY, OrbGpuError, check, lib, orb_connections, orb_frame, orb_kfcull, orb_pointcull,
+                   orb_searchneigh, ptr)
+
+
+class CapacityError(OrbGpuError):
+    """ORB_E_CAPACITY of SearchInNeighbors with the counts the call reported."""
+
+    def __init__(self, code, what, n_ops, n_updated):
+        super().__init__(code, what)
+        self.n_ops, self.n_updated = n_ops, n_updated
 
 
 class Map:
@@ -151,6 +160,66 @@ class Map:
                           0 if b is None else len(b), int(cur_kf), int(monocular), int(apply), ptr(ver), ptr(ob))
         check(self._L.LocalMapping_MapPointCulling(self._h, C.byref(r)), "LocalMapping_MapPointCulling")
         return ver[:n].copy(), ob[:n].copy()
+
+    def SearchInNeighbors(self, matcher, cur_kf, cur, target_ids, targets, kf_desc, Ow, scale_factors, table,
+                          logScaleFactor, th=3.0, apply=True, cap_ops=4096, cap_updated=4096, retry=True):
+        """LocalMapping::SearchInNeighbors (LocalMapping.cc:454-553): every Fuse pass into the targets, the
+        backward pass into the current keyframe and the update of its points, exact across the passes.
+        cur / targets: Frame objects of mpCurrentKeyFrame and vpTargetKFs (ids cur_kf / target_ids, the
+        reference's order); kf_desc: mnId -> mDescriptors of every keyframe live in the handle (a dict or a
+        list with None holes); Ow: n_kf_rows x 3 camera centres by mnId; table: dict of the map-point table's
+        arrays pos, desc, normal, max_dist, min_dist, bad, ref_kf with rows = map-point ids (desc, normal,
+        max_dist, min_dist and bad are written in place on success).  -> dict(nfused (ntargets + 1), ops
+        (k x 6: pass, kind, a, b, kf, idx), updated, n_ref_missing).  On ORB_E_CAPACITY the call is repeated
+        once with the counts it reported (retry)."""
+        Ow = np.ascontiguousarray(Ow, np.float32).reshape(-1, 3)
+        nrows = len(Ow)
+        items = kf_desc.items() if isinstance(kf_desc, dict) else enumerate(kf_desc)
+        rows = {int(k): np.ascontiguousarray(d, np.uint8) for k, d in items if d is not None}
+        dptr = (C.c_void_p * max(nrows, 1))()
+        for k, d in rows.items():
+            if 0 <= k < nrows:
+                dptr[k] = d.ctypes.data if d.size else None
+        tid = np.ascontiguousarray(target_ids, np.int32)
+        nt = len(tid)
+        fr = (orb_frame * max(nt, 1))()
+        for t in range(nt):
+            fr[t] = targets[t].cstruct()
+        fc = cur.cstruct()
+        sf = np.ascontiguousarray(scale_factors, np.float32)
+        want = dict(pos=np.float32, desc=np.uint8, normal=np.float32, max_dist=np.float32, min_dist=np.float32,
+                    bad=np.uint8, ref_kf=np.int32)
+        for k, dt in want.items():
+            a = table[k]
+            assert a.dtype == dt and a.flags["C_CONTIGUOUS"], k   # written in place
+        n = len(table["bad"])
+        nfused = np.zeros(nt + 1, np.int32)
+        caps = (int(cap_ops), int(cap_updated))
+        for attempt in range(2):
+            ops = np.zeros((max(caps[0], 1), 6), np.int32)
+            upd = np.zeros(max(caps[1], 1), np.int32)
+            S = orb_searchneigh(int(cur_kf), C.pointer(fc), nt, ptr(tid) if nt else None, fr, float(th),
+                                float(logScaleFactor), nrows, C.cast(dptr, C.c_void_p), ptr(Ow) if nrows else None,
+                                len(sf), ptr(sf), n, *(ptr(table[k]) if n else None for k in want), int(apply),
+                                caps[0], caps[1], ptr(nfused), ptr(ops), ptr(upd), 0, 0, 0)
+            rc = self._L.LocalMapping_SearchInNeighbors(matcher._h, self._h, C.byref(S))
+            if rc == ORB_E_CAPACITY and attempt == 0 and retry:
+                caps = (max(S.n_ops, 1), max(S.n_updated, 1))
+                continue
+            if rc == ORB_E_CAPACITY:
+                raise CapacityError(rc, "LocalMapping_SearchInNeighbors", S.n_ops, S.n_updated)
+            check(rc, "LocalMapping_SearchInNeighbors")
+            break
+        return dict(nfused=nfused, ops=ops[:S.n_ops].copy(), updated=upd[:S.n_updated].copy(),
+                    n_ref_missing=S.n_ref_missing)
+
+    def last_searchneigh_timings(self):
+        """ms of the last timed SearchInNeighbors (enable_timing): projection, match, descriptor recomputation,
+        final update (HIP events, summed over the passes) and the host replay (wall clock)."""
+        ms = np.zeros(5, np.float32)
+        check(self._L.LocalMapping_SearchInNeighbors_last_timings(self._h, ptr(ms)),
+              "LocalMapping_SearchInNeighbors_last_timings")
+        return ms
 
     def enable_timing(self, on=True):
         check(self._L.Map_enable_timing(self._h, int(on)), "Map_enable_timing")

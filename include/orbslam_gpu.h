@@ -945,6 +945,87 @@ typedef struct orb_gbaapply {
 } orb_gbaapply;
 int LoopClosing_ApplyGlobalBA(ORBmatcher_h h, Map_h map, orb_gbaapply* G);
 
+/* ---- LocalMapping::SearchInNeighbors over the Map handle ----------------------------------
+ * void LocalMapping::SearchInNeighbors()                          LocalMapping.cc:454-553
+ * Every ORBmatcher::Fuse(pKF, vpMapPoints, th) call of one SearchInNeighbors (ORBmatcher.cc:825-975),
+ * the MapPoint::Replace / AddObservation / AddMapPoint they run, and the update of the current
+ * keyframe's points that follows (543-552), as one call that is exact across the targets: a point
+ * that survives a Replace meets the next target with its recomputed descriptor, and isBad(),
+ * IsInKeyFrame(pKF) and Observations() are read on the state the earlier passes left.
+ *
+ * cur / cur_kf = mpCurrentKeyFrame; target[] / target_id[] = vpTargetKFs in the reference's order
+ * (the caller chooses them; a keyframe may be listed more than once, cur_kf may not be listed).
+ * kf_desc[id] = mDescriptors of every keyframe live in the handle (row slots x 32) and Ow[id] =
+ * GetCameraCenter(), indexed by mnId below n_kf_rows.  The map-point table has rows = map-point ids.
+ * Observations() is the handle's count: 2 per stereo slot, 1 per monocular slot (Map_SetKeyFrameKeys).
+ *
+ * 1. Forward passes.  The point list is the current keyframe's row when the call starts.  For each
+ *    target in list order a point is skipped when it is -1, bad (bad[] or replaced earlier in this
+ *    call) or held by an observed slot of the target's row.  The selection per point is that of
+ *    ORBmatcher_Fuse with the point's current descriptor.
+ * 2. The mutations of a pass run in point order (951-971): the chosen slot holds q that is not bad:
+ *    Observations(q) > Observations(p) ? p->Replace(q) : q->Replace(p); it holds a q with bad[q]:
+ *    nothing; it is empty: AddObservation + AddMapPoint.  All three count in nfused.  Replace is
+ *    exactly Map_ReplaceMapPoint.
+ * 3. Every point that survived a Replace gets ComputeDistinctiveDescriptors over its observers in
+ *    ascending keyframe id (the median and tie rule of MapPoint_Update_batch), before the next pass.
+ * 4. Backward pass.  Candidates: the targets in list order, their slots in index order, every held
+ *    point that is not bad and not yet listed (mnFuseCandidateForKF), on the state after the forward
+ *    passes; one Fuse pass into the current keyframe, then step 3.
+ * 5. Every point the current keyframe's row then holds that is not bad: ComputeDistinctiveDescriptors
+ *    and UpdateNormalAndDepth over its observers in ascending id with Ow, ref_kf, the octave of
+ *    ref_kf's observing slot and scale_factors.  A point whose ref_kf is -1, not among its observers
+ *    or whose octave is >= nlevels keeps normal / max_dist / min_dist and counts in n_ref_missing, as
+ *    in LoopClosing_CorrectLoop step 4.  KeyFrame::UpdateConnections stays KeyFrame_UpdateConnections.
+ *
+ * nfused[t] = the return value of pass t (t = ntargets: the backward pass).  ops = the mutations in
+ * execution order, six int32 each: (pass, kind, a, b, kf, idx) with kind 1 = point a added at slot
+ * idx of keyframe kf (b = -1), 2 = a->Replace(b) decided at slot idx of kf (the adapter also moves
+ * mnFound / mnVisible: IncreaseFound / IncreaseVisible of MapPoint::Replace), 3 = point a met the
+ * bad point b there.  updated = the ids whose desc / normal / max_dist / min_dist / bad rows were
+ * written, ascending.  Table rows are written on ORB_OK only; replaced points get bad = 1.
+ * apply != 0: on ORB_OK the handle takes the mutations; apply == 0 leaves it as it was.
+ * ORB_E_CAPACITY when n_ops > cap_ops or n_updated > cap_updated: both counts are set, nothing is
+ * written and nothing is applied.  ORB_E_INVALID, before the device is touched: a missing array, a
+ * negative count, an id that is not live in the handle or >= n_kf_rows, cur_kf among the targets, a
+ * NULL kf_desc of a live keyframe, an orb_frame whose N is not the row's size or with an octave
+ * outside [0, nlevels), a row of cur or of a target with a held but unobserved slot or a held id >=
+ * n, a device-pointer or deferred matcher.  Handles are looked at last: a well-formed call with a
+ * NULL handle answers ORB_E_NODEVICE where no device is visible (ORB_E_INVALID otherwise).
+ * Host pointers; runs on ORBmatcher_stream(h), holds the map handle's lock, synchronous. */
+typedef struct orb_searchneigh {
+    int32_t cur_kf;
+    const orb_frame* cur;
+    int ntargets;
+    const int32_t* target_id;    /* ntargets */
+    const orb_frame* target;     /* ntargets */
+    float th;                    /* 3.0 in the reference */
+    float logScaleFactor;
+    int n_kf_rows;
+    const uint8_t* const* kf_desc; /* n_kf_rows pointers */
+    const float* Ow;             /* n_kf_rows x 3 */
+    int nlevels;
+    const float* scale_factors;  /* nlevels */
+    int n;                       /* map-point table rows */
+    const float* pos;            /* n x 3 */
+    uint8_t* desc;               /* n x 32, in/out */
+    float* normal;               /* n x 3, in/out */
+    float* max_dist;             /* n, in/out */
+    float* min_dist;             /* n, in/out */
+    uint8_t* bad;                /* n, in/out */
+    const int32_t* ref_kf;       /* n */
+    int apply, cap_ops, cap_updated;
+    int32_t* nfused;             /* out ntargets + 1 */
+    int32_t* ops;                /* out cap_ops x 6 */
+    int32_t* updated;            /* out cap_updated */
+    int32_t n_ops, n_updated, n_ref_missing;   /* out */
+} orb_searchneigh;
+int LocalMapping_SearchInNeighbors(ORBmatcher_h h, Map_h map, orb_searchneigh* S);
+/* With Map_enable_timing on: ms5 = projection, match (summed over the passes), descriptor
+ * recomputation (summed), final update (HIP events on the matcher's stream) and the host replay
+ * (wall clock) of the last LocalMapping_SearchInNeighbors; ORB_E_INVALID before the first one. */
+int LocalMapping_SearchInNeighbors_last_timings(Map_h map, float* ms5);
+
 /* DBoW2::FeatureVector (std::map<NodeId, std::vector<unsigned>>) as CSR: strictly ascending
  * node ids, the feature indices of node a at feat[start[a] .. start[a+1]) in insertion order.
  * (Computed by the caller's vocabulary; ORBvoc.txt is not shipped with the reference.) */
@@ -1030,7 +1111,10 @@ int ORBmatcher_SearchByProjection_Sim3(ORBmatcher_h h, const orb_frame* KF, cons
  * skip[i] = !pMP || isBad() || IsInKeyFrame(pKF).  best[i] (out) = keypoint of pKF the
  * reference fuses point i with (bestIdx, 951-971) or -1; *nfused = the return value.  The
  * caller applies 953-969 (Replace / AddObservation) in point order: the selection never
- * depends on those mutations (no occupancy test in Fuse), so the plan is exact. */
+ * depends on those mutations (no occupancy test in Fuse), so the plan is exact -- for this one
+ * call.  Across the calls of one LocalMapping::SearchInNeighbors it is not (Replace recomputes the
+ * survivor's descriptor; skip and Observations() move): LocalMapping_SearchInNeighbors is that
+ * sequence as one exact call. */
 int ORBmatcher_Fuse(ORBmatcher_h h, const orb_frame* KF, const orb_mappoints* pts,
                     const orb_mappoint_geo* geo, const uint8_t* skip, float logScaleFactor, float th,
                     int32_t* best, int* nfused);
