@@ -308,6 +308,8 @@ def lib():
     L.LoopClosing_ApplyGlobalBA.argtypes = [vp, vp, vp]
     L.LocalMapping_SearchInNeighbors.argtypes = [vp, vp, vp]
     L.LocalMapping_SearchInNeighbors_last_timings.argtypes = [vp, vp]
+    L.LoopClosing_SearchAndFuse.argtypes = [vp, vp, vp]
+    L.LoopClosing_SearchAndFuse_last_timings.argtypes = [vp, vp]
     L.orbgpu_unit_set_map_initial_capacity.argtypes = [i32, i32, i32]
     L.orbgpu_unit_set_map_chunk.argtypes = [i32]
     L.orbgpu_unit_set_map_lds_slots.argtypes = [i32]
@@ -449,6 +451,17 @@ class orb_searchneigh(C.Structure):
                 ("bad", C.c_void_p), ("ref_kf", C.c_void_p), ("apply", C.c_int), ("cap_ops", C.c_int),
                 ("cap_updated", C.c_int), ("nfused", C.c_void_p), ("ops", C.c_void_p), ("updated", C.c_void_p),
                 ("n_ops", C.c_int32), ("n_updated", C.c_int32), ("n_ref_missing", C.c_int32)]
+
+
+class orb_loopfuse(C.Structure):
+    _fields_ = [("nkf", C.c_int), ("kf", C.c_void_p), ("frame", C.POINTER(orb_frame)), ("Scw", C.c_void_p),
+                ("nloop", C.c_int), ("loop_pts", C.c_void_p), ("cur_kf", C.c_int32), ("nmatched", C.c_int),
+                ("matched", C.c_void_p), ("th", C.c_float), ("logScaleFactor", C.c_float), ("n_kf_rows", C.c_int),
+                ("kf_desc", C.c_void_p), ("n", C.c_int), ("pos", C.c_void_p), ("normal", C.c_void_p),
+                ("max_dist", C.c_void_p), ("min_dist", C.c_void_p), ("desc", C.c_void_p), ("bad", C.c_void_p),
+                ("apply", C.c_int), ("cap_ops", C.c_int), ("cap_updated", C.c_int), ("nfused", C.c_void_p),
+                ("ops", C.c_void_p), ("updated", C.c_void_p), ("n_ops", C.c_int32), ("n_updated", C.c_int32),
+                ("n_matched_skipped", C.c_int32)]
 
 
 class pose_frame(C.Structure):

@@ -19,4 +19,5 @@ struct Map_t {
     orbgpu::Map map;
     std::mutex mu;   // stands for Map::mMutexMap, KeyFrame::mMutexFeatures / mMutexConnections
     orbgpu::FuseWork fuse;   // LocalMapping_SearchInNeighbors' device buffers (capi_fuse.cpp)
+    orbgpu::LoopFuseWork loopfuse;   // LoopClosing_SearchAndFuse's buffers (capi_loopfuse.cpp)
 };

@@ -68,8 +68,23 @@ struct FuseWork {
     hipEvent_t event(size_t k);
 };
 
+// LoopClosing_SearchAndFuse's state on the Map handle: the device buffers and events, and two pinned
+// host blocks (0: the staged upload of a call, 1: a pass's skip bytes and best[]).
+struct LoopFuseWork {
+    FuseWork dev;
+    void* pin[2] = {};
+    size_t pin_cap[2] = {};
+    ~LoopFuseWork();
+    // at least `bytes` of pinned block i; growing waits for `s` first.  null: out of memory
+    void* pinned(int i, size_t bytes, hipStream_t s);
+};
+
 int fuse_project_launch(const FuseProjDev& P, hipStream_t s);
 int fuse_match_launch(const FuseMatchDev& M, hipStream_t s);
+// The Sim3 form (ORBmatcher.cc:977-1100): kf[t] is target t (kf_of is not read), invz = 1.0 / z, no
+// uRight; the match has no reprojection gate.
+int fuse_project_sim3_launch(const FuseProjDev& P, hipStream_t s);
+int fuse_match_sim3_launch(const FuseMatchDev& M, hipStream_t s);
 // table[id[p]] = rows[start[p] + best[p]] for every p with best[p] >= 0 (32-byte rows)
 int fuse_take_desc_launch(int npts, const int32_t* id, const int32_t* start, const int32_t* best,
                           const uint8_t* rows, uint8_t* table, hipStream_t s);

@@ -6,12 +6,17 @@ row).
 
 The tables are either numpy arrays (host pointers: copied up, corrected, copied back) or torch device
 tensors (device pointers: corrected in place); a call takes all of one kind.  Every table argument is
-changed in place where the call writes it."""
+changed in place where the call writes it.
+
+SearchAndFuse is the loop fusion between the two (the "Start Loop Fusion" block of CorrectLoop and
+LoopClosing::SearchAndFuse) over the same handle; it takes numpy tables only."""
 import ctypes as C
 
 import numpy as np
 
-from ._lib import check, lib, orb_gbaapply, orb_loopcorrect, orb_pointtable, ptr
+from ._lib import (ORB_E_CAPACITY, check, lib, orb_frame, orb_gbaapply, orb_loopcorrect, orb_loopfuse, orb_pointtable,
+                   ptr)
+from .map import CapacityError
 
 _NP = {"f32": np.float32, "i32": np.int32, "u8": np.uint8}
 
@@ -101,6 +106,73 @@ class LoopClosing:
                          self._p(kf_done, "u8", rows), 0, 0, 0, 0)
         check(self._L.LoopClosing_ApplyGlobalBA(self._m._h, self._map._h, C.byref(g)), "LoopClosing_ApplyGlobalBA")
         return dict(n_kf_propagated=g.n_kf_propagated, n_mp_gba=g.n_mp_gba, n_mp_moved=g.n_mp_moved, depth=g.depth)
+
+    def SearchAndFuse(self, kf, frames, Scw, loop_pts, kf_desc, table, logScaleFactor, cur_kf=-1, matched=None,
+                      th=4.0, n_kf_rows=None, apply=True, cap_ops=4096, cap_updated=4096, retry=True):
+        """The "Start Loop Fusion" block of LoopClosing::CorrectLoop and LoopClosing::SearchAndFuse: matched =
+        mvpCurrentMatchedPoints (one id per slot of cur_kf's row, -1 = NULL; None skips that block) merged into
+        the current keyframe, then one Fuse(pKF, Scw, mvpLoopMapPoints, th) with its Replaces per keyframe of
+        kf (ids, any order; the passes run in ascending id), exact across the passes.  frames: their Frame
+        objects; Scw: nkf x 8 float64 (q xyzw, t, s), the CorrectedSim3 of CorrectLoop; loop_pts =
+        mvpLoopMapPoints as ids; kf_desc: mnId -> mDescriptors of every keyframe live in the handle (a dict
+        or a list with None holes; n_kf_rows: the size of that table, default the largest id + 1); table:
+        dict of the map-point table's numpy arrays pos, normal, max_dist, min_dist (read), desc, bad (written
+        in place on success).  -> dict(nfused (nkf, the order of kf), ops (k x 6: pass, kind, a, b, kf, idx),
+        updated, n_matched_skipped).  On ORB_E_CAPACITY the call is repeated once with the counts it
+        reported (retry).  Numpy tables only: a matcher left in device-pointer mode (by a CorrectLoop over
+        torch tensors) or deferred is refused with ORB_E_INVALID."""
+        kf = np.ascontiguousarray(kf, np.int32)
+        nkf = len(kf)
+        Scw = np.ascontiguousarray(Scw, np.float64).reshape(-1, 8)
+        if len(Scw) != nkf or len(frames) != nkf:
+            raise ValueError("kf, frames and Scw: one entry per listed keyframe")
+        loop = np.ascontiguousarray(loop_pts, np.int32)
+        mt = None if matched is None else np.ascontiguousarray(matched, np.int32)
+        items = list(kf_desc.items() if isinstance(kf_desc, dict) else enumerate(kf_desc))
+        rows = {int(k): np.ascontiguousarray(d, np.uint8) for k, d in items if d is not None}
+        nrows = int(n_kf_rows) if n_kf_rows is not None else max([k for k, _ in items], default=-1) + 1
+        dptr = (C.c_void_p * max(nrows, 1))()
+        for k, d in rows.items():
+            if 0 <= k < nrows:
+                dptr[k] = d.ctypes.data if d.size else None
+        fr = (orb_frame * max(nkf, 1))()
+        for k in range(nkf):
+            fr[k] = frames[k].cstruct()
+        want = dict(pos=np.float32, normal=np.float32, max_dist=np.float32, min_dist=np.float32, desc=np.uint8,
+                    bad=np.uint8)
+        for k, dt in want.items():
+            a = table[k]
+            if self._on_device(a) or a.dtype != dt or not a.flags.c_contiguous:
+                raise ValueError(f"table[{k!r}]: a contiguous numpy array of {np.dtype(dt).name}")   # written in place
+        n = len(table["bad"])
+        nfused = np.zeros(max(nkf, 1), np.int32)
+        caps = (int(cap_ops), int(cap_updated))
+        for attempt in range(2):
+            ops = np.zeros((max(caps[0], 1), 6), np.int32)
+            upd = np.zeros(max(caps[1], 1), np.int32)
+            f = orb_loopfuse(nkf, ptr(kf) if nkf else None, fr, ptr(Scw) if nkf else None, len(loop),
+                             ptr(loop) if len(loop) else None, int(cur_kf), 0 if mt is None else len(mt),
+                             None if mt is None else C.c_void_p(mt.ctypes.data), float(th), float(logScaleFactor),
+                             nrows, C.cast(dptr, C.c_void_p), n, *(ptr(table[k]) if n else None for k in want),
+                             int(apply), caps[0], caps[1], ptr(nfused), ptr(ops), ptr(upd), 0, 0, 0)
+            rc = self._L.LoopClosing_SearchAndFuse(self._m._h, self._map._h, C.byref(f))
+            if rc == ORB_E_CAPACITY and attempt == 0 and retry:
+                caps = (max(f.n_ops, 1), max(f.n_updated, 1))
+                continue
+            if rc == ORB_E_CAPACITY:
+                raise CapacityError(rc, "LoopClosing_SearchAndFuse", f.n_ops, f.n_updated)
+            check(rc, "LoopClosing_SearchAndFuse")
+            break
+        return dict(nfused=nfused[:nkf].copy(), ops=ops[:f.n_ops].copy(), updated=upd[:f.n_updated].copy(),
+                    n_matched_skipped=f.n_matched_skipped)
+
+    def last_searchandfuse_timings(self):
+        """ms of the last timed SearchAndFuse (Map.enable_timing): projection, match, descriptor recomputation
+        (HIP events, summed over the passes) and the host replay (wall clock)."""
+        ms = np.zeros(4, np.float32)
+        check(self._L.LoopClosing_SearchAndFuse_last_timings(self._map._h, ptr(ms)),
+              "LoopClosing_SearchAndFuse_last_timings")
+        return ms
 
 
 __all__ = ["LoopClosing"]

@@ -1026,6 +1026,96 @@ int LocalMapping_SearchInNeighbors(ORBmatcher_h h, Map_h map, orb_searchneigh* S
  * (wall clock) of the last LocalMapping_SearchInNeighbors; ORB_E_INVALID before the first one. */
 int LocalMapping_SearchInNeighbors_last_timings(Map_h map, float* ms5);
 
+/* ---- LoopClosing::SearchAndFuse over the Map handle ----------------------------------------
+ * The "Start Loop Fusion" block of LoopClosing::CorrectLoop and
+ * void LoopClosing::SearchAndFuse(const KeyFrameAndPose& CorrectedPosesMap)     LoopClosing.cc
+ * Every ORBmatcher::Fuse(pKF, cvScw, mvpLoopMapPoints, 4, vpReplacePoints) call of one loop closure
+ * (ORBmatcher.cc:977-1100) with the vpReplacePoints[i]->Replace(mvpLoopMapPoints[i]) that follow each
+ * of them, as one call that is exact across the keyframes: a Replace after one keyframe makes points
+ * bad, moves observations and, through ComputeDistinctiveDescriptors at the end of MapPoint::Replace,
+ * changes the descriptor the survivor is matched with in the next keyframe.
+ *
+ * kf[] / frame[] / Scw[] = the keyframes of CorrectedSim3 with their corrected Sim3 (q xyzw, t, s:
+ * the CorrectedSim3 output of LoopClosing_CorrectLoop), in any order; the passes run in ascending
+ * keyframe id (the id-order rule for the pointer-keyed KeyFrameAndPose map).  The frames carry keysUn,
+ * desc, N, grid bounds, intrinsics and scaleFactors; Tcw is not read and may be NULL.  loop_pts =
+ * mvpLoopMapPoints as map-point ids (-1 = NULL, skipped).  cur_kf / matched[] = mpCurrentKF and
+ * mvpCurrentMatchedPoints as ids, one per slot of its row (-1 = NULL); matched == NULL skips step 0.
+ * kf_desc[id] = mDescriptors of every keyframe live in the handle, by mnId below n_kf_rows.  The
+ * map-point table has rows = map-point ids; pos, normal, max_dist and min_dist are read only (nothing
+ * in this part of the reference moves them), desc and bad are in/out.
+ *
+ * 0. For each slot i of cur_kf's row in index order with L = matched[i] >= 0: the slot holds c: c == L
+ *    is nothing (Replace returns at once), otherwise c->Replace(L) (kind 2).  The slot is empty and L is
+ *    not in the row: AddMapPoint + AddObservation + ComputeDistinctiveDescriptors(L) (kind 1).
+ *    Deliberate difference: the slot is empty and another slot of the row already holds L: the entry
+ *    is skipped and counted in n_matched_skipped (the reference would leave slot i holding L without an
+ *    observation, a state the handle refuses, see Map_SetMapPointMatches).
+ * 1. Per listed keyframe: cvScw = Converter::toCvMat(g2oScw) (R = q.toRotationMatrix() in double, the
+ *    entries (float)(s * R_ij) and (float)t_i), then scw, Rcw, tcw, Ow as ORBmatcher_Fuse_Sim3 takes them.
+ * 2. skip[i] = loop_pts[i] < 0 || bad (bad[] or replaced earlier in this call) || held by the
+ *    keyframe's row, taken when the pass starts (spAlreadyFound = pKF->GetMapPoints()).
+ * 3. The selection per point is that of ORBmatcher_Fuse_Sim3 with the point's current descriptor.
+ * 4. In point order: the chosen slot holds q that is not bad: vpReplacePoint[i] = q; it holds a bad q:
+ *    nothing (kind 3); it is empty: AddObservation + AddMapPoint (kind 1; a later point of the pass that
+ *    chooses that keypoint finds this one there).  All three count in nfused.
+ * 5. After the pass, in point order: vpReplacePoint[i]->Replace(loop_pts[i]) (kind 2), exactly
+ *    Map_ReplaceMapPoint.  A q that an earlier Replace of this loop already made bad is replaced again
+ *    as in the reference: nothing moves, the op is logged and the survivor's descriptor is recomputed.
+ * 6. Every survivor of step 0 / of a pass gets ComputeDistinctiveDescriptors over its observers in
+ *    ascending keyframe id (the median and tie rule of MapPoint_Update_batch) before the next pass.
+ *
+ * nfused[k] = the return value of the Fuse into kf[k].  ops = the mutations in execution order, six
+ * int32 each: (pass, kind, a, b, kf, idx) with pass = the index into kf[] (-1: step 0) and the kinds
+ * of orb_searchneigh: 1 = point a added at slot idx of keyframe kf (b = -1), 2 = a->Replace(b) decided
+ * at that slot (IncreaseFound / IncreaseVisible of MapPoint::Replace are the adapter's), 3 = point a met
+ * the bad point b there.  updated = the ids whose desc or bad row was written, ascending.  Table rows
+ * are written on ORB_OK only; replaced points get bad = 1.  apply != 0: on ORB_OK the handle takes the
+ * mutations; apply == 0 and every failure leave the handle and the table as they were.
+ * ORB_E_CAPACITY when n_ops > cap_ops or n_updated > cap_updated: both counts are set, nothing is
+ * written and nothing is applied.  ORB_E_INVALID, before the device is touched: a missing array, a
+ * negative count, a listed id that is not live in the handle, >= n_kf_rows or named twice, loop_pts
+ * holding an id twice or an id >= n, a matched[] id >= n or bad when the call starts, an orb_frame
+ * whose N is not the row's size or with an octave outside [0, nlevels), nmatched different from
+ * cur_kf's row size, a row of a listed keyframe (or of cur_kf in step 0) with a held but unobserved
+ * slot or a held id >= n, a NULL kf_desc of a live keyframe, a non-finite Scw or s <= 0, a
+ * device-pointer or deferred matcher.  What needs no handle is checked first and the handles are
+ * looked at last: a well-formed call with a NULL handle answers ORB_E_NODEVICE where no device is
+ * visible (ORB_E_INVALID otherwise).
+ * Host pointers; runs on ORBmatcher_stream(h), holds the map handle's lock, synchronous. */
+typedef struct orb_loopfuse {
+    int nkf;
+    const int32_t* kf;           /* nkf */
+    const orb_frame* frame;      /* nkf */
+    const double* Scw;           /* nkf x 8: q xyzw, t, s */
+    int nloop;
+    const int32_t* loop_pts;     /* nloop */
+    int32_t cur_kf;
+    int nmatched;
+    const int32_t* matched;      /* nmatched, or NULL: no step 0 */
+    float th;                    /* 4 in the reference */
+    float logScaleFactor;
+    int n_kf_rows;
+    const uint8_t* const* kf_desc; /* n_kf_rows pointers */
+    int n;                       /* map-point table rows */
+    const float* pos;            /* n x 3 */
+    const float* normal;         /* n x 3 */
+    const float* max_dist;       /* n */
+    const float* min_dist;       /* n */
+    uint8_t* desc;               /* n x 32, in/out */
+    uint8_t* bad;                /* n, in/out */
+    int apply, cap_ops, cap_updated;
+    int32_t* nfused;             /* out nkf, in the order of kf[] */
+    int32_t* ops;                /* out cap_ops x 6 */
+    int32_t* updated;            /* out cap_updated */
+    int32_t n_ops, n_updated, n_matched_skipped;   /* out */
+} orb_loopfuse;
+int LoopClosing_SearchAndFuse(ORBmatcher_h h, Map_h map, orb_loopfuse* F);
+/* With Map_enable_timing on: ms4 = projection, match (summed over the passes), descriptor
+ * recomputation (summed) (HIP events on the matcher's stream) and the host replay (wall clock) of the
+ * last LoopClosing_SearchAndFuse; ORB_E_INVALID before the first one. */
+int LoopClosing_SearchAndFuse_last_timings(Map_h map, float* ms4);
+
 /* DBoW2::FeatureVector (std::map<NodeId, std::vector<unsigned>>) as CSR: strictly ascending
  * node ids, the feature indices of node a at feat[start[a] .. start[a+1]) in insertion order.
  * (Computed by the caller's vocabulary; ORBvoc.txt is not shipped with the reference.) */
